@@ -17,7 +17,10 @@ asynchronously beside the next step's forward (--gather overlap: rounds 1-5).
 When invoked plainly with --gpus N > 1 the parent process imports nothing that touches the GPU: it starts N fresh
 children (one per GPU, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in their environment) and relays rank 0's line.
 
-Rank 0 prints ONE JSON line: value = whole-job poses/s, plus
+Rank 0 prints ONE JSON line: value = whole-job poses/s, ms_per_step = milliseconds of one timed step.  A plain run does
+nothing else: it sets up, runs `warmup` untimed and `steps` timed forwards, writes the outputs of the last timed step when
+--dump-outputs DIR is given (DIR/poses_3d.npy, float32; the inputs and weights are seeded, so two builds given the same
+arguments can be compared output for output), and prints the line.  With --full the line also carries
   roofline     -- dominant kernel (h2_stack_kernel: every GEMM of the FPT block stack in one persistent launch): FLOPs per
                   launch / mean launch duration, measured live with HIP events on the launch stream (mpl_profile_start/stop)
                   over a whole region of `steps` forwards.  The default fp32 path computes those GEMMs on the fp16 matrix
@@ -29,6 +32,8 @@ Rank 0 prints ONE JSON line: value = whole-job poses/s, plus
                   repeats the entry for the other engines (bf16 at V = 8, the small-batch engine at one frame).
   cpu_baseline -- the oracle (a port of the reference's CPU PyTorch path) timed on this box's host cores, headline
                   workload first, BASELINE.md section 4's other configurations under `others`.
+  parity       -- this run's output against the oracle on 64 poses;
+  extra        -- the repeated headline region, the secondary engines, shapes and configurations (--no-extra skips most).
 """
 from __future__ import annotations
 
@@ -54,19 +59,31 @@ FULL = dict(pose_3d_emb_learnable=True, confidence_input_as_third=True, input_ra
             multiple_spatial_blocks=True, add_3D_pos_encoding_to_rays=True)
 
 
+def _positive(s):
+    n = int(s)
+    if n < 1:
+        raise argparse.ArgumentTypeError("must be >= 1")
+    return n
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=50)
-    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--steps", type=_positive, default=50, help="timed forwards")
+    ap.add_argument("--warmup", type=int, default=10, help="untimed forwards before them")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure and check everything else: roofline and per-kernel times, parity "
+                         "against the oracle, CPU baseline, secondary engines and configurations (off: the headline line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step to DIR/<name>.npy (float32, at most 64 MB)")
     ap.add_argument("--batch", type=int, default=1024, help="poses per GPU per step")
     ap.add_argument("--views", type=int, default=4)
     ap.add_argument("--depth", type=int, default=12)
     ap.add_argument("--flagset", choices=("chosen", "full", "kptok"), default="chosen",
                     help="chosen / full: the two shipped YAML families; kptok: CHOSEN + FPT_blocks_view_keypoint_tokens (the joints x "
                          "views token grid, 17 V tokens of width 32: BASELINE configs[4] with --views 31 --batch 256)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the secondary measurements (other configs / engines)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the secondary measurements (other configs / engines)")
     ap.add_argument("--force-dist", action="store_true",
                     help="run the rank code path (process group + all-gather) even at one GPU")
     ap.add_argument("--gather", choices=("stream", "overlap"), default="stream",
@@ -194,25 +211,27 @@ def spt_flops_per_forward(flags, batch):
     return per_view * flags["num_views"] * batch
 
 
-def timed_steps(model, batches, steps, warmup, lifter=None, global_batch=None):
+def timed_steps(model, batches, steps, warmup, lifter=None, global_batch=None, outputs=None):
     """EXACTLY `steps` forwards between two (barrier +) device synchronisations.  With a lifter every step also starts
-    its all-gather; the wait for step i's exchange is issued after step i+1's forward has been enqueued."""
+    its all-gather; the wait for step i's exchange is issued after step i+1's forward has been enqueued.  A list passed as
+    `outputs` receives what the last timed step returned (with a lifter: the gathered whole-batch poses)."""
     import torch
     import torch.distributed as dist
 
     def run(n):
-        pending = None
+        pending, out = None, None
         for i in range(n):
             P, R, C = batches[i % len(batches)]
             if lifter is None:
-                model(P, rays=R, centers=C)
+                out = model(P, rays=R, centers=C)
             else:
                 h = lifter.lift_shard(P, R, C, batch=global_batch)
                 if pending is not None:
-                    pending.wait()
+                    out = pending.wait()
                 pending = h
         if pending is not None:
-            pending.wait()
+            out = pending.wait()
+        return out
 
     with torch.no_grad():
         run(warmup)
@@ -220,11 +239,31 @@ def timed_steps(model, batches, steps, warmup, lifter=None, global_batch=None):
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        run(steps)
+        out = run(steps)
         if lifter is not None:
             dist.barrier()
         torch.cuda.synchronize()
-        return time.perf_counter() - t0
+        dt = time.perf_counter() - t0
+    if outputs is not None:
+        outputs.append(out)
+    return dt
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, out):
+    """`out` (the (B, 17, 3) poses of one step) -> path/poses_3d.npy in float32.  Beyond DUMP_LIMIT_BYTES a fixed sample of
+    rows is written instead (seeded: the same rows in every run of the same shape, in batch order)."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    rows = out.shape[0]
+    row_bytes = 4 * out[0].numel()
+    if rows * row_bytes > DUMP_LIMIT_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(rows, DUMP_LIMIT_BYTES // row_bytes, replace=False))
+        out = out[torch.from_numpy(keep).to(out.device)]
+    np.save(os.path.join(path, "poses_3d.npy"), out.detach().float().cpu().numpy())
 
 
 MIN_LEG_STEPS, LEG_REGIONS = 20, 5
@@ -348,26 +387,54 @@ def run_rank(a):
         os.environ.setdefault("MASTER_PORT", str(_free_port()))
         dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)   # backend "nccl" IS RCCL on ROCm
         lifter = ShardedLifter(model, gather=a.gather)
-    split = a.precision in ("fp32", "bf16") and model._x3_supported()
     # a few distinct resident batches (per rank: pre-sharded inputs) so that no step can reuse a cached result
     batches = [make_batch(a.batch, a.views, dev, seed=1000 + rank, step=s) for s in range(4)]
 
-    dt = timed_steps(model, batches, a.steps, a.warmup, lifter, world * a.batch)
+    last = []
+    dt = timed_steps(model, batches, a.steps, a.warmup, lifter, world * a.batch, outputs=last)
     if dist is not None:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     ms_per_step = dt / a.steps * 1e3
     value = world * a.batch * a.steps / dt
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, last[0])
+    del last
 
     result = None
     if rank == 0:
-        result = report(a, model, flags, batches, dev, world, value, ms_per_step, split, dist is not None)
+        result = headline(a, world, value, ms_per_step, dist is not None)
+        if a.full:
+            split = a.precision in ("fp32", "bf16") and model._x3_supported()
+            result.update(report(a, model, flags, batches, dev, world, value, split, dist is not None))
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
         print(json.dumps(result), file=json_out, flush=True)
+
+
+def headline(a, world, value, ms_per_step, used_dist):
+    """The fields of the result line that the timed region alone determines (a plain run prints these and nothing else)."""
+    line = {"value": round(value, 1), "unit": "poses/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+            "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None}
+    if a.flagset == "kptok":
+        return dict({"metric": "poses/sec (V=%d, J=17, batch=%d per GPU) fp32, joints x views token grid" % (a.views, a.batch)},
+                    **line, dtype="f32", data="synthetic", rccl_ranks=world if used_dist else 0,
+                    config={"workload": "large-view stress: V=%d J=17 batch=%d fp32, CHOSEN + FPT_blocks_view_keypoint_tokens "
+                                        "(%d-token grid), depth %d" % (a.views, a.batch, 17 * a.views, a.depth),
+                            "global_batch": world * a.batch,
+                            "parallelism": "single GPU" if not used_dist else "dp%d" % world})
+    prec = "bf16" if a.precision == "bf16" else "fp32"
+    return dict({"metric": "poses/sec (V=%d, J=17, batch=%d per GPU) %s" % (a.views, a.batch, prec)},
+                **line, dtype="bf16" if a.precision == "bf16" else "f32", data="synthetic", rccl_ranks=world if used_dist else 0,
+                config={"workload": "%s config: V=%d J=17 batch=%d %s, %s flag set, depth %d, DIM 32, heads 8"
+                                    % ("CMU Panoptic" if a.views == 8 else "Human3.6M", a.views, a.batch, prec, a.flagset.upper(), a.depth),
+                        "global_batch": world * a.batch,
+                        "parallelism": ("dp%d: pre-sharded batch, 1 RCCL all_gather of (B/G,17,3) per step (%s)" % (world, {
+                            "stream": "ordered into the compute stream between two forwards",
+                            "overlap": "async, beside the next forward"}[a.gather])) if used_dist else "single GPU"})
 
 
 def kptok_roofline(model, flags, batch, views, batches, n_prof=20):
@@ -406,11 +473,10 @@ def kptok_roofline(model, flags, batch, views, batches, n_prof=20):
                 share_of_kernel_time=round(att_ms / sum(t for t, _ in prof.values()), 3), traffic=None)
 
 
-def kptok_report(a, model, flags, batches, dev, world, value, ms_per_step, used_dist):
-    """`--flagset kptok`: the bench line of the joints x views token grid (roofline: kptok_roofline)."""
+def kptok_report(a, model, flags, batches):
+    """`--flagset kptok --full`: the rest of the bench line of the joints x views token grid (roofline: kptok_roofline)."""
     import torch
     from oracle import mpl_oracle
-    N = 17 * a.views
     roof = kptok_roofline(model, flags, a.batch, a.views, batches, max(a.steps, 20))
     P, R, C = batches[0]
     nb = min(16, a.batch)
@@ -422,24 +488,18 @@ def kptok_report(a, model, flags, batches, dev, world, value, ms_per_step, used_
     ref = mpl_oracle.forward(sd, flags, cpu(P, nb), cpu(R, nb), cpu(C, nb))
     mx, nw = mpl_oracle.rel_errors(got, ref)
     return {
-        "metric": "poses/sec (V=%d, J=17, batch=%d per GPU) fp32, joints x views token grid" % (a.views, a.batch),
-        "value": round(value, 1), "unit": "poses/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-        "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
-        "data": "synthetic", "rccl_ranks": world if used_dist else 0,
-        "config": {"workload": "large-view stress: V=%d J=17 batch=%d fp32, CHOSEN + FPT_blocks_view_keypoint_tokens (%d-token grid), depth %d"
-                               % (a.views, a.batch, N, a.depth), "global_batch": world * a.batch,
-                   "parallelism": "single GPU" if not used_dist else "dp%d" % world},
         "roofline": roof, "cpu_baseline": None,
         "parity": dict(max_scaled=float("%.3e" % mx), norm_wise=float("%.3e" % nw), poses=nb, tol=1e-4), "extra": {},
     }
 
 
-def report(a, model, flags, batches, dev, world, value, ms_per_step, split, used_dist):
+def report(a, model, flags, batches, dev, world, value, split, used_dist):
+    """--full: everything of the bench line beyond the headline fields, each measured after the timed region."""
     import torch
     from openmpl_amd import cabi
     from oracle import mpl_oracle
     if a.flagset == "kptok":
-        return kptok_report(a, model, flags, batches, dev, world, value, ms_per_step, used_dist)
+        return kptok_report(a, model, flags, batches)
     # ---- per-kernel time, measured live with HIP events on the launch stream: a WHOLE region of `steps` forwards run like the
     # timed one (same batches, back to back, warm), with every launch bracketed -- not a handful of forwards behind an idle gap
     P, R, C = batches[0]
@@ -655,18 +715,6 @@ def report(a, model, flags, batches, dev, world, value, ms_per_step, split, used
             extra.update(dist_and_dp_extras(a, model, batches, dev))
 
     return {
-        "metric": "poses/sec (V=%d, J=17, batch=%d per GPU) %s" % (a.views, a.batch, "bf16" if a.precision == "bf16" else "fp32"),
-        "value": round(value, 1), "unit": "poses/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-        "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "bf16" if a.precision == "bf16" else "f32", "data": "synthetic",
-        "rccl_ranks": world if used_dist else 0,
-        "config": {"workload": "%s config: V=%d J=17 batch=%d %s, %s flag set, depth %d, DIM 32, heads 8"
-                               % ("CMU Panoptic" if a.views == 8 else "Human3.6M", a.views, a.batch,
-                                  "bf16" if a.precision == "bf16" else "fp32", a.flagset.upper(), a.depth),
-                   "global_batch": world * a.batch,
-                   "parallelism": ("dp%d: pre-sharded batch, 1 RCCL all_gather of (B/G,17,3) per step (%s)" % (world, {
-                       "stream": "ordered into the compute stream between two forwards", "overlap": "async, beside the next forward"}[a.gather]))
-                   if used_dist else "single GPU"},
         "roofline": roof, "rooflines": rooflines(roof, extra, a), "cpu_baseline": cpu_base, "parity": parity, "extra": extra,
     }
 

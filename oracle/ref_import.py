@@ -1,8 +1,8 @@
 """Import the *reference* model (build container only -- /root/reference never travels).
 
-TEST INFRASTRUCTURE ONLY.  Used by ``tests/golden/make_golden.py`` (fixture
-generation) and by the CPU tests that validate the oracle against the live
-reference when ``/root/reference`` exists.  ``timm`` is absent from the image;
+TEST INFRASTRUCTURE ONLY.  Used by ``tests/golden/make_golden.py`` and
+``tests/golden/make_golden_reference.py`` (fixture generation); the tests read
+the fixtures and never import the reference.  ``timm`` is absent from the image;
 ``multiview_mpl.py:13-16`` only *executes* ``DropPath`` (identity in eval), so six
 stub modules are inserted into ``sys.modules`` before the file is loaded
 (SURVEY.md section 8c).

@@ -11,6 +11,8 @@
 #include <cstring>
 #include <vector>
 
+#include <hip/hip_runtime_api.h>
+
 #include "mpl_hip.h"
 
 static int failures = 0;
@@ -23,6 +25,12 @@ static int failures = 0;
     } while (0)
 
 int main() {
+    // the calls below hand the library host pointers, and its device code is empty bundles here: it must never meet a device
+    int devices = 0;
+    if (hipGetDeviceCount(&devices) == hipSuccess && devices > 0) {
+        std::fprintf(stderr, "host_driver: %d GPU(s) visible, this job needs none (run.sh sets HIP_VISIBLE_DEVICES=-1)\n", devices);
+        return 2;
+    }
     EXPECT(mpl_hip_abi_version() == MPL_HIP_ABI_VERSION);
     for (int c = -9; c <= 1; ++c) {
         const char* s = mpl_hip_error_string(c);

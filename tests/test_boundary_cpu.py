@@ -10,7 +10,7 @@ import torch
 from openmpl_amd import cabi, detrng
 from openmpl_amd import build as mpl_build
 from openmpl_amd.multiview_mpl import MultiView_MPL, MultiView_MPL_G, get_multiview_mpl_net
-from oracle import mpl_oracle, ref_import
+from oracle import mpl_oracle
 from tests.golden.cases import CASES, MICRO
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -29,17 +29,34 @@ def test_state_dict_layout_matches_reference_layout(case):
     assert list(got) == list(m.state_dict().keys())
 
 
-@pytest.mark.skipif(not ref_import.available(), reason="/root/reference not present")
 @pytest.mark.parametrize("name", ["chosen_v4_b8_l2", "full_v4_b8_l2", "kadkhod_v3_b3_l2", "deep_head_v3_b3_l2",
                                   "conf_add_v3_b3_l2", "linear_wmean_v3_b3_l2"])
 def test_loads_live_reference_state_dict_strict_and_same_key_order(name):
+    """The reference module's state_dict layout (key order, shapes) and parameter count for these flags were recorded by
+    tests/golden/make_golden_reference.py (reference_layouts.json); a state_dict of that layout must load strictly."""
     from tests.golden.cases import BY_NAME
     flags = BY_NAME[name]["flags"]
-    ref = ref_import.build_reference(dict(flags, drop_path_rate=0.1))
+    ref = _reference_layouts()["layouts"][name]
+    ref_sd = _state_dict_of_layout(ref["state_dict"])
     ours = MultiView_MPL(**flags)
-    assert list(ref.state_dict().keys()) == list(ours.state_dict().keys())
-    ours.load_state_dict(ref.state_dict(), strict=True)
-    assert sum(p.numel() for p in ours.parameters()) == sum(p.numel() for p in ref.parameters())
+    assert list(ref_sd.keys()) == list(ours.state_dict().keys())
+    ours.load_state_dict(ref_sd, strict=True)
+    assert sum(p.numel() for p in ours.parameters()) == ref["n_parameters"]
+
+
+def _reference_layouts():
+    import json
+    with open(os.path.join(ROOT, "tests", "golden", "reference_layouts.json")) as f:
+        return json.load(f)
+
+
+def _state_dict_of_layout(layout):
+    """A state_dict with the recorded key order and shapes (the values do not matter: load_state_dict checks the layout)."""
+    return {k: torch.zeros(shape) for k, shape in layout}
+
+
+def _namespace(d):
+    return types.SimpleNamespace(**{k: _namespace(v) if isinstance(v, dict) else v for k, v in d.items()})
 
 
 def _cfg(**net):
@@ -154,24 +171,24 @@ def test_detrng_is_stable():
     assert [round(float(t), 12) for t in v] == [round(float(t), 12) for t in detrng.uniform01(0, "x", 5)[:3]]
 
 
-@pytest.mark.skipif(not ref_import.available(), reason="/root/reference not present")
 def test_shipped_yaml_configs_build_the_reference_module_layout():
-    """valid_mpl.py:162 path: every YAML under MPL/configs, loaded through the reference's own core/config.py
-    (update_config, config.py:359-373; easydict stand-in), must construct a module with the reference's parameter
-    names, order and shapes, the same num_views, and load the reference's state_dict strictly."""
-    yamls = ref_import.shipped_yamls()
-    assert len(yamls) == 4
-    ref_mod = ref_import.load_reference_module()
+    """valid_mpl.py:162 path: every YAML under MPL/configs, as the reference's own core/config.py resolves it (update_config,
+    config.py:359-373), must construct a module with the reference's parameter names, order and shapes, the same
+    num_views, and load the reference's state_dict strictly.  The resolved configs and the layout of the module the
+    reference's get_multiview_mpl_net builds from each were recorded by tests/golden/make_golden_reference.py."""
+    configs = _reference_layouts()["configs"]
+    assert len(configs) == 4
     seen = set()
-    for y in yamls:
-        cfg = ref_import.load_reference_config(y)
+    for rec in configs:
+        y = rec["yaml"]
+        cfg = _namespace(dict(MODEL=rec["MODEL"], DATASET=rec["DATASET"], NETWORK=rec["NETWORK"]))
         assert cfg.MODEL == "multiview_mpl"
-        ref = ref_mod.get_multiview_mpl_net(cfg, is_train=False)
+        rs = _state_dict_of_layout(rec["state_dict"])
         ours = get_multiview_mpl_net(cfg, is_train=False)
-        rs, os_ = ref.state_dict(), ours.state_dict()
+        os_ = ours.state_dict()
         assert list(rs.keys()) == list(os_.keys()), y
         assert [tuple(v.shape) for v in rs.values()] == [tuple(v.shape) for v in os_.values()], y
-        assert ours.features.num_views == ref.features.num_views
+        assert ours.features.num_views == rec["num_views"]
         assert ours.features.depth == cfg.NETWORK.TRANSFORMER_DEPTH
         ours.load_state_dict(rs, strict=True)
         assert ours.features._unsupported is None, (y, ours.features._unsupported)

@@ -91,7 +91,7 @@ def test_bench_spawns_its_own_ranks(tmp_path):
     box N = 1 still goes through the same rank code path (process group of size 1 when --force-dist is given)."""
     n = min(2, torch.cuda.device_count())
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "3", "--warmup", "1",
-                        "--no-extra", "--no-cpu-baseline", "--force-dist"], cwd=ROOT, stdout=subprocess.PIPE,
+                        "--full", "--no-extra", "--no-cpu-baseline", "--force-dist"], cwd=ROOT, stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, timeout=900)
     assert r.returncode == 0, r.stderr.decode(errors="replace")[-4000:]
     import json

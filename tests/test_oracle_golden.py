@@ -1,11 +1,15 @@
 """Pin the oracle: it must reproduce every golden vector captured from the reference."""
+import json
+import os
+
+import numpy as np
 import pytest
 import torch
 
-from oracle import mpl_oracle, ref_import
+from oracle import mpl_oracle
 from openmpl_amd import detrng
 from tests.golden.cases import CASES, MICRO
-from tests.util import golden_inputs, golden_state_dict, load_golden
+from tests.util import GOLDEN_DIR, golden_inputs, golden_state_dict, load_golden
 
 ALL = [c["name"] for c in CASES] + [MICRO["name"]]
 TOL = 2e-6   # oracle and reference run the same ATen ops; observed <= 2e-7
@@ -51,22 +55,23 @@ def test_block_schedule_last_block_twice():
     assert mpl_oracle.block_schedule(2, True) == [(0, True), (0, False), (1, True), (1, False), (1, False)]
 
 
-@pytest.mark.skipif(not ref_import.available(), reason="/root/reference not present (GPU box)")
 @pytest.mark.parametrize("name", ["chosen_v4_b8_l2", "full_v4_b8_l2", "conf_attnw_v3_b3_l2", "kadkhod_v3_b3_l2"])
 def test_oracle_matches_live_reference_on_fresh_inputs(name):
-    """Different weights/inputs than the fixtures: guards against over-fitting to the goldens."""
-    g = load_golden(name)
-    flags = g["flags"]
-    m = ref_import.build_reference(dict(flags, drop_path_rate=0.1))
-    detrng.fill_module_(m, seed=99)
-    p, r, c = detrng.make_inputs(6, flags["num_views"], seed=123)
+    """Different weights/inputs than the fixtures: guards against over-fitting to the goldens.  The reference's outputs
+    for them were recorded by tests/golden/make_golden_reference.py (reference_fresh.npz); weights and inputs are
+    regenerated from the same detrng seeds."""
+    flags = load_golden(name)["flags"]
+    fresh = np.load(os.path.join(GOLDEN_DIR, "reference_fresh.npz"))
+    meta = json.loads(bytes(fresh["meta"]).decode())
+    shapes = mpl_oracle.param_shapes(flags)
+    sd = {k: torch.from_numpy(v) for k, v in detrng.make_state_dict(shapes, seed=meta["wseed"]).items()}
+    p, r, c = detrng.make_inputs(meta["batch"], flags["num_views"], seed=meta["iseed"])
     P = [torch.from_numpy(x) for x in p]
     R = [torch.from_numpy(x) for x in r]
     C = [torch.from_numpy(x) for x in c]
-    with torch.no_grad():
-        ref = m([x.clone() for x in P], rays=R, centers=C)
-    out = mpl_oracle.forward(m.state_dict(), flags, P, R, C)
-    if isinstance(ref, tuple):
-        ref, out = ref[0], out[0]
+    ref = torch.from_numpy(fresh[name])
+    out = mpl_oracle.forward(sd, flags, P, R, C)
+    if isinstance(out, tuple):
+        out = out[0]
     mx, nw = mpl_oracle.rel_errors(out, ref)
     assert mx < TOL and nw < TOL

@@ -1,6 +1,6 @@
 #!/bin/bash
 # One GPU session for the tracked profiles/ of a round:
-#     bash tools/gpu_profile_session.sh r03                         headline workload (python bench.py)
+#     bash tools/gpu_profile_session.sh r03                         headline workload (python bench.py --full)
 #     bash tools/gpu_profile_session.sh r03 cmu_v8_bf16 "--precision bf16 --views 8 --depth 2"    another workload
 #   1. bench line (N=1)                                             -> gpurun_out/prof_$TAG[_$SUF]/bench.json
 #   2. rocprofv3 kernel trace + stats of the SAME command           -> .../trace/
@@ -16,13 +16,13 @@ mkdir -p $O; export TMPDIR=/tmp
 cd $R
 python -c "from openmpl_amd import build; print(build.source_hash())" > $O/srchash.txt
 if [ -z "$SUF" ]; then
-  python bench.py > $O/bench.log 2>&1
+  python bench.py --full > $O/bench.log 2>&1
 else
-  python bench.py $ARGS --no-extra --no-cpu-baseline > $O/bench.log 2>&1
+  python bench.py $ARGS --full --no-extra --no-cpu-baseline > $O/bench.log 2>&1
 fi
 grep '^{"metric"' $O/bench.log | tail -1 > $O/bench.json
 cd /tmp
-CMD="python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extra $ARGS"
+CMD="python3 $R/bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-extra $ARGS"
 echo "$CMD" | sed "s#$R/##" > $O/cmd.txt
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o t -- $CMD > $O/trace.log 2>&1
 P="rocprofv3 --kernel-trace --output-format csv"

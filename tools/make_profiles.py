@@ -43,7 +43,7 @@ if os.path.exists("%s/bench.json" % G):
     except Exception:
         bj = None
 cmdline = open("%s/cmd.txt" % G).read().strip() if os.path.exists("%s/cmd.txt" % G) else \
-    "python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extra"
+    "python3 bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-extra"
 
 out = open(stem + "pmc_summary.txt", "w")
 
