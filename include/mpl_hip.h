@@ -218,7 +218,7 @@ int mpl_x3_debug_buffer(void *device_buffer);
  * workgroups, h2_stack_kernel); 1 = one launch per GEMM (results agree to <= 4 ulp, each mode is bitwise
  * deterministic).  Bits 1-2: 0 = the stack picks its stage by the shape of the launch (fp16x2: teams that own two or more row
  * tiles walk PAIRS of tiles, h2_stack2_kernel; bf16: always one tile at a time), 1 / 2 = force the one- / two-tile stage
- * (bitwise the same poses; bf16: h2_stackp_kernel, pairs in every phase).  Bit 3: no
+ * (fp16x2 only; bitwise the same poses).  Bit 3: no
  * small-batch engine (sm_stack.hip: stacks of up to 80 token rows run every GEMM on the whole chip, the activations handed
  * over as {value, tag} pairs, exact fp32 MFMA on the nn.Linear tensors in place; two fp32 engines, <= 1e-6 apart).  Bit 4: the 16-row teams in
  * the ring form (h2_stackn_kernel) instead of the direct-W form (h2_stackd_kernel).  Bits 5-6: row-narrow teams: 0 = by the
@@ -236,7 +236,7 @@ enum {
     MPL_FORM_UNPACKED = 0,        /* no packed operands: one launch per GEMM on the fp32-MFMA engine (ln_gemm.hip / the D = 32 path) */
     MPL_FORM_SMALL = 1,           /* sm_stack_kernel: up to 80 token rows, every GEMM on the whole chip */
     MPL_FORM_TEAMS = 2,           /* h2_stack_kernel<NP>: one 64-row tile per team step */
-    MPL_FORM_PAIRS = 3,           /* h2_stack2_kernel<2> (A/B: h2_stackp_kernel<1>): pairs of row tiles */
+    MPL_FORM_PAIRS = 3,           /* h2_stack2_kernel<2>: pairs of row tiles (fp16x2 operands only) */
     MPL_FORM_ROWS32 = 4,          /* h2_stackn_kernel<2>: 32-row teams */
     MPL_FORM_ROWS16 = 5,          /* h2_stackn_kernel<2>: 16-row teams, ring form (A/B, or A operand too large for LDS) */
     MPL_FORM_ROWS16_DIRECT = 6,   /* h2_stackd_kernel<2>: 16-row teams, direct-W form */

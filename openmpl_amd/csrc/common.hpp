@@ -12,8 +12,8 @@
 
 namespace mpl {
 
-// Environment switches of measurement scripts (geometry overrides, phase timing, alternative kernels).  They exist in laboratory
-// builds only (-DMPL_LAB, tools/build_variants.sh): the product library never changes behaviour because a variable happens to be set.
+// Environment switches of measurement scripts (today MPL_SPT_ABL, the SPT kernel's ablations).  They exist in laboratory builds
+// only (-DMPL_LAB, tools/build_variants.sh): the product library never changes behaviour because a variable happens to be set.
 inline const char* lab_getenv(const char* name) {
 #ifdef MPL_LAB
     return getenv(name);
@@ -23,14 +23,6 @@ inline const char* lab_getenv(const char* name) {
 #endif
 }
 
-#ifndef MPL_LAB
-#ifdef MPL_SPLIT_MIX
-#error "MPL_SPLIT_MIX is a laboratory switch: build with -DMPL_LAB"
-#endif
-#endif
-#ifndef MPL_SPLIT_MIX
-#define MPL_SPLIT_MIX 1     // 0: the lo part of the two-term fp16 split by convert / subtract / convert (rounds 3-5); bitwise the same
-#endif
 // x = hi + lo in fp16: hi = fp16(x), lo = fp16(x - hi) (RNE; the residual is exact in fp32; subnormal results are kept) -- the
 // operand split of the fp16x2 engines (h2_phase.hpp, spt.hip).  8 values per lane = one MFMA fragment per part.
 // Round 6: the lo part is ONE v_fma_mix{lo,hi}_f16 per value (fp16(hi * -1.0 + x): hi read as fp16, the fma in fp32, one rounding
@@ -41,7 +33,6 @@ inline const char* lab_getenv(const char* name) {
 typedef _Float16 mpl_f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 mpl_f16x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void split2_f16(const float (&x)[8], mpl_f16x8& hi, mpl_f16x8& lo) {
-#if MPL_SPLIT_MIX
     typedef unsigned u4 __attribute__((ext_vector_type(4)));
     u4 h, l;
 #pragma unroll
@@ -56,12 +47,6 @@ __device__ __forceinline__ void split2_f16(const float (&x)[8], mpl_f16x8& hi, m
     }
     hi = __builtin_bit_cast(mpl_f16x8, h);
     lo = __builtin_bit_cast(mpl_f16x8, l);
-#else
-#pragma unroll
-    for (int i = 0; i < 8; ++i) hi[i] = (_Float16)x[i];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) lo[i] = (_Float16)(x[i] - (float)hi[i]);
-#endif
 }
 
 

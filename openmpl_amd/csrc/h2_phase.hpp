@@ -28,13 +28,12 @@ constexpr int H2_MAX_WGS = 1024;
 constexpr int H2_ATT_TS = 3 * BN + 4;        // row stride (floats) of the q | k | v tile of the generic attention epilogue
 constexpr float H2_SA = 1024.0f;             // scale of a normalised LayerNorm input (|z| <= sqrt(K): fine up to K = 2048)
 constexpr int H2_TRV = 5;                    // fp32 vectors of length N behind the fragments: c | sc | sw | bound | so
-// ---- laboratory switches.  The product library is built WITHOUT -DMPL_LAB: every switch below then has the one value the
-// shipped kernels were measured and tested with, and a stray -DH2_* on the command line is a compile error instead of a
-// silently different (or, for H2_ABL, deliberately WRONG) library.  tools/build_variants.sh passes -DMPL_LAB together with the
-// switch it varies; the values and what they do are unchanged from rounds 3-5.
+// ---- laboratory instruments.  The product library is built WITHOUT -DMPL_LAB: both switches below are then 0, and a stray
+// -DH2_* on the command line is a compile error instead of a silently different (for H2_ABL, deliberately WRONG) library.
+// tools/build_variants.sh passes -DMPL_LAB together with the switch it varies.  (The design alternatives measured in rounds 3-5
+// were removed from the sources once decided; HISTORY.md keeps their results.)
 #ifndef MPL_LAB
-#if defined(H2_DBG) || defined(H2_ABL) || defined(H2_DW_PIN) || defined(H2_WT_AUX) || defined(H2_WSPLIT) || defined(H2_R2_AB) || \
-    defined(H2_R2_AB2) || defined(H2_TAIL_LOOP) || defined(H2_KPS2)
+#if defined(H2_DBG) || defined(H2_ABL)
 #error "H2_* experiment switches are laboratory-only: build with -DMPL_LAB (tools/build_variants.sh does)"
 #endif
 #endif
@@ -44,37 +43,10 @@ constexpr int H2_TRV = 5;                    // fp32 vectors of length N behind 
 #ifndef H2_ABL
 #define H2_ABL 0        // bench-only ablations (results are GARBAGE): 1 no B fragment reads, 2 no DMA refill, 4 no A fragment reads, 8 no MFMA, 16 no LayerNorm conversion, 32 no barrier, 64 W out of a hot L2
 #endif
-#ifndef H2_DW_PIN
-#define H2_DW_PIN 1     // direct-W form: pin the MFMA / load interleave of a stage (sched_group_barrier)
-#endif
-#ifndef H2_WT_AUX
-#define H2_WT_AUX 17    // cache policy of the hand-off stores: 17 = sc0 sc1 (write-through), 16 = sc1
-#endif
-#ifndef H2_WSPLIT
-#define H2_WSPLIT 1     // W pieces per stage and wave: 0 = 1 (waves 0..3) / 4 (waves 4, 5) / 3 (waves 6, 7); 1 = 2 / 3 / 2
-#endif
-#ifndef H2_R2_AB
-#define H2_R2_AB 1      // bf16 pair form: A pieces by the waves 4..7 (see h2_phase)
-#endif
-#define H2_RP_WC0 (H2_R2_AB ? 4 : 1)      // W pieces per wave role of the bf16 pair form
-#define H2_RP_WC1 (H2_R2_AB ? 1 : 4)
-#define H2_RP_WC2 (H2_R2_AB ? 0 : 3)
-#ifndef H2_R2_AB2
-#define H2_R2_AB2 0     // the same duty for the two-tile stage of the fp16x2 engine (h2_stack2_kernel)
-#endif
-#define H2_R2_WC0 (H2_R2_AB2 ? 4 : 1)      // W pieces per wave role of the two-tile stage (the waves 0..3 carry four A pieces)
-#define H2_R2_WC1 (H2_R2_AB2 ? 1 : 4)
-#define H2_R2_WC2 (H2_R2_AB2 ? 0 : 3)
-#define H2_WC0 (H2_WSPLIT == 1 ? 2 : 1)
-#define H2_WC1 (H2_WSPLIT == 1 ? 3 : 4)
-#define H2_WC2 (H2_WSPLIT == 1 ? 2 : 3)
-#ifndef H2_TAIL_LOOP
-#define H2_TAIL_LOOP 1
-#endif
-#ifndef H2_KPS2
-#define H2_KPS2 1      // 1: one barrier per TWO stages: it publishes two stages at once, the refill then targets 5 stages ahead (one
-                       // ring slot of slack); 0: a barrier in front of every stage, refill 6 stages ahead
-#endif
+// W pieces per stage that a wave of each role requests (role 0: waves 0..3, role 1: waves 4, 5, role 2: waves 6, 7).  One-tile
+// stage: 2 / 3 / 2.  Two-tile stage (h2_stack2_kernel): the waves 0..3 carry four A pieces, so 1 / 4 / 3.
+constexpr int H2_WC0 = 2, H2_WC1 = 3, H2_WC2 = 2;
+constexpr int H2_R2_WC0 = 1, H2_R2_WC1 = 4, H2_R2_WC2 = 3;
 
 // stages (k steps) of a K-wide operand: NP = 2 (fp16 hi | lo) one 32-deep k-tile per stage; NP = 1 (bf16) a PAIR of k-tiles per
 // stage -- the second KiB of every 2-KiB fragment slot holds the odd k-tile instead of the lo part, so both engines move the
@@ -136,12 +108,13 @@ enum { H2_EPI_BIAS = 0, H2_EPI_GELU = 1, H2_EPI_RES = 2, H2_EPI_ATT = 3 };
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t h2_rsrc(const void* base) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, 0x7fffffff, 0x00020000);
 }
+// hand-off stores: `wt` = write-through (cache policy 17 = sc0 sc1), else plain
 __device__ __forceinline__ void h2_st16(bool wt, void* base, unsigned off, const u32x4& w) {
-    if (wt) __builtin_amdgcn_raw_buffer_store_b128(w, h2_rsrc(base), off, 0, H2_WT_AUX);
+    if (wt) __builtin_amdgcn_raw_buffer_store_b128(w, h2_rsrc(base), off, 0, 17);
     else __builtin_amdgcn_raw_buffer_store_b128(w, h2_rsrc(base), off, 0, 0);
 }
 __device__ __forceinline__ void h2_st8(bool wt, void* base, unsigned off, const u32x2& h) {
-    if (wt) __builtin_amdgcn_raw_buffer_store_b64(h, h2_rsrc(base), off, 0, H2_WT_AUX);
+    if (wt) __builtin_amdgcn_raw_buffer_store_b64(h, h2_rsrc(base), off, 0, 17);
     else __builtin_amdgcn_raw_buffer_store_b64(h, h2_rsrc(base), off, 0, 0);
 }
 __device__ __forceinline__ u32x4 h2_ld16_l2(const void* base, unsigned off) {
@@ -275,7 +248,7 @@ __device__ __forceinline__ void h2_attention(bool WT, float* T, float* SC, int t
 // workgroup arrives when its outputs are written.  Returns false when the wait timed out (error words set, nothing computed).
 // WC = W pieces this wave requests per stage (2 for the waves 0..3, 3 for the waves 4, 5, 2 for the waves 6, 7): a template
 // parameter, so that neither the requests nor the counted waits need a branch in the k loop.
-// RT = row tiles per workgroup.  RT = 2 (h2_stack2_kernel: teams that own two or more row tiles): the stage carries the A
+// RT = row tiles per workgroup.  RT = 2 (h2_stack2_kernel, fp16x2 only: teams that own two or more row tiles): the stage carries the A
 // pieces of TWO row tiles (8 row groups, 16 KiB) against the same 18 KiB of W -- 34 KiB for 54 MFMAs per SIMD instead of 26 KiB
 // for 27, the W fragments are read from LDS once for both tiles -- in a ring of 4 with one barrier per stage (a stage is as long
 // as two of the RT = 1 stages, so that IS the two-stage barrier period).  `tm` then counts pairs of row tiles.  The arithmetic of
@@ -305,7 +278,7 @@ __device__ __forceinline__ bool h2_phase(const H2Args& a, char* smem, int tid, i
     constexpr int NST = RT == 1 ? H2_NST : 4;
     constexpr int APW = 2 * RT;                  // A pieces a wave 0..3 requests per A stage
     static_assert(NST * STAGE <= H2_VEC, "ring too large");
-    static_assert(RT == 1 || (RT == 2 && CHAIN && (NP == 1 || (EPI != H2_EPI_ATT && NPASS <= 2))), "two row tiles per stage: proj / fc1 / fc2 of a stack (NP = 1: every phase)");
+    static_assert(RT == 1 || (RT == 2 && CHAIN && NP == 2 && EPI != H2_EPI_ATT && NPASS <= 2), "two row tiles per stage: proj / fc1 / fc2 of the fp16x2 stack");
     constexpr bool RAWX = LNF && NP == 2;        // the A operand is the raw fp32 rows, normalised + split in the k loop
     // P2: one barrier per TWO stages.  At the barrier in front of an even stage e every wave has its pieces of the stages
     // <= e + 2 landed and has finished reading the fragments of the stages <= e, so stage e may refill the slot of stage e - 1
@@ -313,15 +286,12 @@ __device__ __forceinline__ bool h2_phase(const H2Args& a, char* smem, int tid, i
     // published: the LayerNorm operand stays RAW in LDS and every wave that multiplies it normalises + splits its lane's eight
     // values in registers (both waves of a row group do the same arithmetic; the in-place conversion by the requesting wave
     // that this replaced needed every barrier and made the waves 0..3 the slow half of the stage).
-    constexpr bool P2 = H2_KPS2 != 0 && RT == 1;
+    constexpr bool P2 = RT == 1;
     constexpr int DIST = P2 ? NST - 1 : NST;
     constexpr bool LEAD = NTW == H2_T0;          // waves 0..3 (slots 0..4): multiply first, load afterwards; bring the epilogue vectors
     // A pieces: the waves 0..3 (the second row tile's pieces moved to the waves 4..7, with the 2 / 3 / 2 W split: measured 0 at
-    // M = 8192 on the fp16x2 engine, tools/ab_rt2.sh, and removed again).  AB (bf16 pair form): the waves 4..7, which request at
-    // the HEAD of a stage, bring ALL A pieces (four each) and the waves 0..3, which request behind their product rows, W only:
-    // the A strips come from beyond L2 (their producers store write-through) and need the longer flight
-    constexpr bool AB = RT == 2 && (NP == 1 ? H2_R2_AB != 0 : H2_R2_AB2 != 0);
-    constexpr bool HAS_A = (AB ? !LEAD : LEAD) && ACT;
+    // M = 8192 on the fp16x2 engine, tools/ab_rt2.sh, and removed again)
+    constexpr bool HAS_A = LEAD && ACT;
     const bool WT = CHAIN && !a.plain;
     const int lane = tid & 63;
     // DW: every wave works for row group rg_lo (the two multiplying waves sit on different SIMDs)
@@ -345,16 +315,14 @@ __device__ __forceinline__ bool h2_phase(const H2Args& a, char* smem, int tid, i
     }
 
     // ---- DMA pieces of this wave.  W (18 per stage): waves 4, 5 pieces 0..2 / 3..5, waves 6, 7 pieces 6, 7 / 8, 9, wave
-    // w < 4 pieces 10 + 2 w, 11 + 2 w (H2_WSPLIT 0: 4 / 4 / 3 / 3 and one each).  A (8 per A stage): waves 0..3 the two pieces
+    // w < 4 pieces 10 + 2 w, 11 + 2 w.  A (8 per A stage): waves 0..3 the two pieces
     // of row group `wave`.  (Moving ALL W pieces to the waves 4..7 paid while the waves 0..3 also converted the LayerNorm
     // operand in place, -3 %; it costs 1-5 % now.)
     // RT = 2: the waves 0..3 carry four A pieces, so they take one W piece each and the waves 4..7 four / three (the 1 / 4 / 3 split)
-    constexpr bool WS1 = H2_WSPLIT == 1 && RT == 1;
-    const int w_first = AB ? (LEAD ? 4 * wave : 12 + wave)
-                      : WS1 ? (LEAD ? 10 + 2 * wave : (wave < 6 ? 3 * (wave - 4) : 6 + 2 * (wave - 6)))
-                            : (LEAD ? 14 + wave : (wave < 6 ? 4 * (wave - 4) : 8 + 3 * (wave - 6)));
-    static_assert(AB ? (LEAD ? WC == 4 : (WC == 1 || WC == 0))
-                     : WS1 ? (LEAD ? WC == 2 : (WC == 3 || WC == 2)) : (LEAD ? WC == 1 : (WC == 3 || WC == 4)), "W pieces per wave");
+    const int w_first = RT == 1 ? (LEAD ? 10 + 2 * wave : (wave < 6 ? 3 * (wave - 4) : 6 + 2 * (wave - 6)))
+                                : (LEAD ? 14 + wave : (wave < 6 ? 4 * (wave - 4) : 8 + 3 * (wave - 6)));
+    static_assert(RT == 1 ? (LEAD ? WC == H2_WC0 : (WC == H2_WC1 || WC == H2_WC2))
+                          : (LEAD ? WC == H2_R2_WC0 : (WC == H2_R2_WC1 || WC == H2_R2_WC2)), "W pieces per wave");
     constexpr int w_cnt = WC;
     unsigned voW = (unsigned)(lane * 16 + w_first * 1024);
     // A source offsets of this lane.  Packed operand: 16 B per lane and part.  fp32 rows (LNF): the lane's 4 + 4 columns of
@@ -1012,7 +980,7 @@ __device__ __forceinline__ bool h2_phase(const H2Args& a, char* smem, int tid, i
                     mm(n, 0, 0);
                     if constexpr (more) Bb[j][n][0] = dw_ld(src + (n * 2 + 0) * 1024);
                 }
-                if constexpr (more && H2_DW_PIN) {
+                if constexpr (more) {        // pin the MFMA / load interleave of the stage
                     __builtin_amdgcn_sched_group_barrier(0x008, NTW, 0);
 #pragma unroll
                     for (int i = 0; i < 2 * NTW; ++i) {
@@ -1040,7 +1008,7 @@ __device__ __forceinline__ bool h2_phase(const H2Args& a, char* smem, int tid, i
             const int rest = T - u0;
             // each tail inside a loop that runs exactly once behind an opaque trip count: with the back edge the accumulators are
             // loop-carried values that end where they started, which keeps the allocator from renaming them MFMA by MFMA
-            // (out-of-place v_mfma + hundreds of spills; the same device as H2_TAIL_LOOP of the ring form)
+            // (out-of-place v_mfma + hundreds of spills)
             int tail_rep = 1;
             asm volatile("" : "+s"(tail_rep));
             if (rest == PD) {
@@ -1080,19 +1048,8 @@ __device__ __forceinline__ bool h2_phase(const H2Args& a, char* smem, int tid, i
     // T - t is in [NST, NST + U - 1] and congruent to T, i.e. to 0 or NPASS, modulo U: two possible tail lengths
     constexpr int TAIL_A = (NST + U - 1) / U * U;
     constexpr int TAIL_B = (NST - NPASS + U - 1) / U * U + NPASS;
-    // H2_TAIL_LOOP: the straight-line tail sits inside a loop that runs exactly once behind an opaque trip count.  With the
-    // back edge the accumulators are loop-carried values that must end where they started, which keeps the allocator from
-    // renaming them MFMA by MFMA (out-of-place v_mfma + spills of the pass that is idle) towards the epilogue's assignments.
-    constexpr bool TAIL_LOOP = H2_TAIL_LOOP && RT == 2 && NP == 1;
-    int tail_rep = 1;
-    if (TAIL_LOOP) asm volatile("" : "+s"(tail_rep));
-    if (T - t == TAIL_A) {
-        do tail(tail, std::integral_constant<int, TAIL_A>{}, std::integral_constant<int, 0>{});
-        while (TAIL_LOOP && --tail_rep);
-    } else {
-        do tail(tail, std::integral_constant<int, TAIL_B>{}, std::integral_constant<int, 0>{});
-        while (TAIL_LOOP && --tail_rep);
-    }
+    if (T - t == TAIL_A) tail(tail, std::integral_constant<int, TAIL_A>{}, std::integral_constant<int, 0>{});
+    else tail(tail, std::integral_constant<int, TAIL_B>{}, std::integral_constant<int, 0>{});
     }
 
     // ------------------------------------------------------------------------------------------ epilogue
@@ -1663,73 +1620,6 @@ __global__ __launch_bounds__(512, 2) void h2_stack_kernel(const H2StackArgs s) {
     }
 }
 
-// The stack for teams that own two or more row tiles, bf16 operands (NP = 1): a team walks PAIRS of row tiles through EVERY
-// phase -- with one part per operand the fragments of a two-tile stage and the three accumulator sets of the qkv phase fit the
-// register file together, so the qkv + attention phase and the two-pass fc1 run the two-tile stage too (every W k-tile pair is
-// fetched and read from LDS once for both tiles).  Same poses as h2_stack_kernel<1> bit for bit.
-template <int NP>
-__global__ __launch_bounds__(512, 2) void h2_stackp_kernel(const H2StackArgs s) {
-    extern __shared__ __attribute__((aligned(1024))) char smem[];
-    const int tid = threadIdx.x;
-    const int wave_s = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int G = s.G, D = s.D;
-    int team, tn;
-    {
-        const int b = blockIdx.x;
-        team = (b & 7) + 8 * ((b >> 3) / G);
-        tn = (b >> 3) % G;
-        if (team >= s.n_teams) return;
-    }
-    if (tid == 0) *reinterpret_cast<volatile unsigned*>(smem + H2_FAIL) = 0u;
-    h2_publish_xcd(s, team, tid);
-    int plain = 0, seen = 0;       // plain hand-off stores once the team is known to sit on one XCD (h2_publish_xcd)
-    __syncthreads();
-    const int n_pairs = (s.n_tiles + 1) >> 1;
-    for (int pair0 = team; pair0 < n_pairs; pair0 += s.n_teams) {
-        unsigned need = 0;
-        for (int ph = 0; ph < s.n_phases; ++ph, need += G) {
-            if (!seen && ph >= 2) {       // the proj phase has seen every partner arrive: the team's placement word is complete
-                plain = __builtin_amdgcn_readfirstlane(h2_team_on_one_xcd(s, team));
-                seen = 1;
-            }
-            int wvp = wave_s, pair = pair0, tnp = tn;
-            asm volatile("" : "+s"(wvp), "+s"(pair), "+s"(tnp));
-            int tidp = wvp * 64 + (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-            asm volatile("" : "+v"(tidp));
-            const int wv = wvp;
-            unsigned* ctr = s.counters + 2 * pair;       // the arrival counter of the pair = the one of its first row tile
-            const char* const* w = s.w[ph >> 2];
-            bool ok = true;
-            if (s.inject > 0 && ph == s.inject && pair == 0 && tnp == 0) return;     // fault injection (test hook)
-            switch (ph & 3) {
-                case 0: {
-                    H2Args a = h2_args_qkv<NP>(s, w[0], D, G, plain);
-                    if (wv < 4) ok = h2_phase<H2_EPI_ATT, true, 3, H2_T0, true, H2_RP_WC0, 2, NP>(a, smem, tidp, wv, 0, pair, tnp, ctr, need);
-                    else if (wv < 6) ok = h2_phase<H2_EPI_ATT, true, 3, NT - H2_T0, true, H2_RP_WC1, 2, NP>(a, smem, tidp, wv, H2_T0, pair, tnp, ctr, need);
-                    else ok = h2_phase<H2_EPI_ATT, true, 3, NT - H2_T0, true, H2_RP_WC2, 2, NP>(a, smem, tidp, wv, H2_T0, pair, tnp, ctr, need);
-                    break;
-                }
-                case 2: {
-                    H2Args a = h2_args_fc1<NP>(s, w[2], D, G, plain);
-                    if (wv < 4) ok = h2_phase<H2_EPI_GELU, true, 2, H2_T0, true, H2_RP_WC0, 2, NP>(a, smem, tidp, wv, 0, pair, tnp, ctr, need);
-                    else if (wv < 6) ok = h2_phase<H2_EPI_GELU, true, 2, NT - H2_T0, true, H2_RP_WC1, 2, NP>(a, smem, tidp, wv, H2_T0, pair, tnp, ctr, need);
-                    else ok = h2_phase<H2_EPI_GELU, true, 2, NT - H2_T0, true, H2_RP_WC2, 2, NP>(a, smem, tidp, wv, H2_T0, pair, tnp, ctr, need);
-                    break;
-                }
-                default: {
-                    const bool fc2 = (ph & 3) == 3;
-                    H2Args a = h2_args_res<NP>(s, fc2 ? w[3] : w[1], fc2, D, G, plain);
-                    if (wv < 4) ok = h2_phase<H2_EPI_RES, false, 1, H2_T0, true, H2_RP_WC0, 2, NP>(a, smem, tidp, wv, 0, pair, tnp, ctr, need);
-                    else if (wv < 6) ok = h2_phase<H2_EPI_RES, false, 1, NT - H2_T0, true, H2_RP_WC1, 2, NP>(a, smem, tidp, wv, H2_T0, pair, tnp, ctr, need);
-                    else ok = h2_phase<H2_EPI_RES, false, 1, NT - H2_T0, true, H2_RP_WC2, 2, NP>(a, smem, tidp, wv, H2_T0, pair, tnp, ctr, need);
-                    break;
-                }
-            }
-            if (!ok) return;
-        }
-    }
-}
-
 // The same stack for teams that own TWO OR MORE row tiles (M > 64 x the number of teams the chip holds: the FULL flag set at
 // B = 1024, eight views, B >= 2048): a team walks PAIRS of row tiles.  proj, fc1 and fc2 run the two-tile stage (h2_phase RT = 2:
 // every W k-tile is fetched and read once for both tiles); the qkv + attention phase, whose three accumulator sets leave no
@@ -1737,7 +1627,7 @@ __global__ __launch_bounds__(512, 2) void h2_stackp_kernel(const H2StackArgs s) 
 // h2_stack_kernel (tested: the batch-split and shard equalities of tests/test_gpu_parity.py cross the switch).
 template <int NP>
 __global__ __launch_bounds__(512, 2) void h2_stack2_kernel(const H2StackArgs s) {
-    static_assert(NP == 2, "the six-step pair form of the fp16x2 engine (NP = 1: h2_stackp_kernel)");
+    static_assert(NP == 2, "the two-tile stage exists in the fp16x2 engine only");
     extern __shared__ __attribute__((aligned(1024))) char smem[];
     const int tid = threadIdx.x;
     const int wave_s = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1972,13 +1862,6 @@ __global__ __launch_bounds__(512, 2) void h2_stackd_kernel(const H2StackArgs s) 
     }
 }
 
-// the kernel of the pair form: six steps per block application for fp16x2 operands, every phase on pairs for bf16 operands
-template <int NP>
-static auto h2_pair_kernel() -> void (*)(const H2StackArgs) {
-    if constexpr (NP == 2) return h2_stack2_kernel<2>;
-    else return h2_stackp_kernel<1>;
-}
-
 // ---------------------------------------------------------------------------------------------- host side of the stack launch
 unsigned long long* h2_debug_buffer();       // h2_gemm.hip (A/B switches and test hooks shared by both engines)
 int h2_spin_log2();
@@ -2003,13 +1886,11 @@ static H2Form h2_stack_form(int M, int D, int n_tok, int cus) {
     H2Form f{0, 4, 0};
     const int rpt = h2_rows_per_tile(n_tok), n_tiles = (M + rpt - 1) / rpt, G = D / BN;
     const int cap = cus / G;
-    // more row tiles than teams the chip holds: teams walk PAIRS of row tiles with the two-tile stage.  h2_row_tiles(): A/B switch
-    // (mpl_x3_stack_mode bits 1, 2).  bf16 operands (NP = 1): one tile at a time by default -- the pair form of every phase
-    // (h2_stackp_kernel) was built and measured in round 5 and is NOT faster (V = 8, B = 1024: 332 against 311 us for depth 2):
-    // the 34-KiB stage leaves a ring of four, too shallow for the flight time of the A strips, and a wave's product rows and its
-    // requests do not overlap
+    // more row tiles than teams the chip holds (fp16x2 operands): teams walk PAIRS of row tiles with the two-tile stage.
+    // h2_row_tiles(): A/B switch (mpl_x3_stack_mode bits 1, 2).  bf16 operands (NP = 1) always go one tile at a time (a pair
+    // form of every phase was measured in round 5 and was slower, HISTORY.md)
     const int force = h2_row_tiles();
-    f.pairs = (force == 2 || (force == 0 && NP == 2 && n_tiles > cap)) ? 1 : 0;
+    f.pairs = (NP == 2 && (force == 2 || (force == 0 && n_tiles > cap))) ? 1 : 0;
     // row-narrow teams (fp16x2 operands): when whole-tile teams would leave compute units idle, a tile is split into sub-tiles of
     // 16 or 32 rows -- the narrowest form that still gives every workgroup a compute unit of its own.  Sequences must not straddle
     // row groups: 16 a multiple of n_tok
@@ -2048,9 +1929,11 @@ static int h2_launch_stack(float* x, unsigned short* x16, int M, int D, int n_to
             return MPL_E_LAUNCH;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)h2_stack_kernel<NP>, 512, H2_LDS_BYTES) != hipSuccess || per_cu < 1)
             return MPL_E_UNSUPPORTED;
-        const void* pk = (const void*)h2_pair_kernel<NP>();
-        if (hipFuncSetAttribute(pk, hipFuncAttributeMaxDynamicSharedMemorySize, H2_LDS_BYTES) != hipSuccess) return MPL_E_LAUNCH;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pk, 512, H2_LDS_BYTES) != hipSuccess || per_cu < 1) return MPL_E_UNSUPPORTED;
+        if constexpr (NP == 2) {
+            const void* pk = (const void*)h2_stack2_kernel<2>;
+            if (hipFuncSetAttribute(pk, hipFuncAttributeMaxDynamicSharedMemorySize, H2_LDS_BYTES) != hipSuccess) return MPL_E_LAUNCH;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pk, 512, H2_LDS_BYTES) != hipSuccess || per_cu < 1) return MPL_E_UNSUPPORTED;
+        }
         resident[dev].store(cus, std::memory_order_release);
     }
     H2StackArgs a;
@@ -2074,7 +1957,7 @@ static int h2_launch_stack(float* x, unsigned short* x16, int M, int D, int n_to
     // (tools/wt_ab.py): bf16 engine -2 .. -4 % stack time (its stage is bound by the L2 -> LDS path, half of its bytes are
     // activations), row-narrow teams -2 %, headline fp16x2 stack 0 % in time but 9 % less fabric traffic (2.43 -> 2.22 GB per
     // launch, L2 hit rate 80 -> 89 %: profiles/r05_gemm_traffic.json); FULL on the two-tile stage +1.7 % (slower): write-through there
-    a.plain_ok = (!h2_write_through_always() && (NP == 1 || !pairs)) ? 1 : 0;
+    a.plain_ok = (!h2_write_through_always() && !pairs) ? 1 : 0;
     const int n_units_n = a.rgs == 4 ? n_units : a.n_tiles * (4 / a.rgs);
     a.n_teams = n_units_n < cap ? n_units_n : cap;
     if (a.n_teams * a.G > H2_MAX_WGS) a.n_teams = H2_MAX_WGS / a.G;
@@ -2108,8 +1991,12 @@ static int h2_launch_stack(float* x, unsigned short* x16, int M, int D, int n_to
         rc = MPL_OK;
         if (form.direct) rc = launch_h2d_stack(a, ((a.n_teams + 7) / 8) * 8 * a.G, s);
         else if (a.rgs != 4) rc = launch_h2n_stack(a, ((a.n_teams + 7) / 8) * 8 * a.G, s);
-        else if (pairs) hipLaunchKernelGGL(h2_pair_kernel<NP>(), dim3(((a.n_teams + 7) / 8) * 8 * a.G), dim3(512), H2_LDS_BYTES, s, a);
-        else hipLaunchKernelGGL(h2_stack_kernel<NP>, dim3(((a.n_teams + 7) / 8) * 8 * a.G), dim3(512), H2_LDS_BYTES, s, a);
+        else if constexpr (NP == 2) {
+            if (pairs) hipLaunchKernelGGL(h2_stack2_kernel<2>, dim3(((a.n_teams + 7) / 8) * 8 * a.G), dim3(512), H2_LDS_BYTES, s, a);
+            else hipLaunchKernelGGL(h2_stack_kernel<2>, dim3(((a.n_teams + 7) / 8) * 8 * a.G), dim3(512), H2_LDS_BYTES, s, a);
+        } else {
+            hipLaunchKernelGGL(h2_stack_kernel<1>, dim3(((a.n_teams + 7) / 8) * 8 * a.G), dim3(512), H2_LDS_BYTES, s, a);
+        }
         if (rc == MPL_OK) rc = hip_check_launch();
     }
     if (hipEventRecord(ev, s) != hipSuccess) return MPL_E_LAUNCH;

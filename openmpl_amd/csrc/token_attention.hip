@@ -266,12 +266,12 @@ __device__ __forceinline__ void attend_rows(const float* __restrict__ base, size
     }
 }
 
-template <int HD4>
+// head dim 8 (head dim 4 takes the key-pair kernel below)
 __global__ __launch_bounds__(256) void token_attention_long_kernel(const float* __restrict__ qkv,
                                                                     float* __restrict__ out, int n_tok, int D, int H,
                                                                     float scale) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
-    constexpr int HD = 4 * HD4, R = 3;
+    constexpr int HD4 = 2, HD = 4 * HD4, R = 3;
     const int nthr = blockDim.x;                     // 64 * ceil(n_tok / 192): every wave gets the same number of row slots
     const int sq = blockIdx.x / H, h = blockIdx.x % H;
     const size_t ld = (size_t)3 * D;
@@ -296,7 +296,7 @@ __global__ __launch_bounds__(256) void token_attention_long_kernel(const float* 
     }
 }
 
-// ---- head dim 4, keys in PAIRS: the kernel above spends 12 VALU instructions per score (4 for q.k, subtract, exp, max,
+// ---- head dim 4, keys in PAIRS: the kernel above (one key at a time) spends 12 VALU instructions per score (4 for q.k, subtract, exp, max,
 // sum, 4 for p.v) at one instruction per 4 cycles and wave -- it is VALU-issue bound.  Here two keys share every multiply-add:
 // K and V live in LDS as [pair]{x_j, x_j+1, y_j, y_j+1, z_j, z_j+1, w_j, w_j+1}, the scores, the exponent arguments, the row
 // sum and the output accumulate as 2-vectors (packed fp32 instructions); the two halves of the output / row sum (even and odd
@@ -456,15 +456,11 @@ int launch_token_attention(const float* qkv, int n_seq, int n_tok, int dim, int 
         // its K / V reads with two others is cheaper than a resident wave more.  The result of a row does not depend on any of this.
         int waves = (n_tok + 47) / 48;
         waves = waves < 1 ? 1 : (waves > 4 ? 4 : waves);
-        static const bool no_pairs = lab_getenv("MPL_ATT_NOPAIRS") != nullptr;      // bench-only A/B switch
-        if (hd == 4 && !no_pairs)
+        if (hd == 4)
             hipLaunchKernelGGL(token_attention_long_p4_kernel, dim3(n_seq * heads), dim3(64 * waves), (size_t)((n_tok + 1) / 2) * 64, s,
                                qkv, out, n_tok, dim, heads, sc);
-        else if (hd == 4)
-            hipLaunchKernelGGL((token_attention_long_kernel<1>), dim3(n_seq * heads), dim3(64 * waves), lds, s, qkv, out, n_tok,
-                               dim, heads, sc);
         else
-            hipLaunchKernelGGL((token_attention_long_kernel<2>), dim3(n_seq * heads), dim3(64 * waves), lds, s, qkv, out, n_tok,
+            hipLaunchKernelGGL(token_attention_long_kernel, dim3(n_seq * heads), dim3(64 * waves), lds, s, qkv, out, n_tok,
                                dim, heads, sc);
         return hip_check_launch();
     }
@@ -473,8 +469,7 @@ int launch_token_attention(const float* qkv, int n_seq, int n_tok, int dim, int 
     ProfScope prof(MPL_K_ATTENTION, s);
     {
         const size_t seq_bytes = (size_t)n_tok * (3 * dim + 4) * 4 + (size_t)heads * n_tok * n_tok * 4;
-        static const bool force_v1 = lab_getenv("MPL_ATT_V1") != nullptr;   // bench-only A/B switch
-        if (seq_bytes <= 150 * 1024 && !force_v1) {
+        if (seq_bytes <= 150 * 1024) {
             int spw = (int)((56 * 1024) / seq_bytes);
             if (spw < 1) spw = 1;
             if (spw > 8) spw = 8;

@@ -679,10 +679,9 @@ def test_bf16_operand_bytes_match_the_definition():
 
 @pytest.mark.parametrize("name,B", [("chosen_v8_b4_l2", 200), ("chosen_v4_b8_l2", 1030), ("chosen_v5_b19_l2", 40), ("full_v4_b8_l2", 70)])
 def test_bf16_launch_forms_are_bitwise_the_same(name, B):
-    """The bf16 stack has three forms of the same arithmetic: the persistent launch with one row tile per team step (default),
-    the pair form of every phase (h2_stackp_kernel: built and measured in round 5, not faster, kept behind the A/B switch) and
-    one launch per GEMM.  Same k order, same product order, same epilogue: the poses must agree bit for bit -- also across
-    ragged last tiles, an odd tile count (a pair without its second tile) and the 60-row tiles of five views."""
+    """The bf16 stack has two forms of the same arithmetic: the persistent launch with one row tile per team step (default,
+    also when forced) and one launch per GEMM.  Same k order, same product order, same epilogue: the poses must agree bit for
+    bit -- also across ragged last tiles, an odd tile count and the 60-row tiles of five views."""
     lib = cabi.load()
     m, g = _model(name)
     m.set_matmul_precision("bf16")
@@ -690,14 +689,14 @@ def test_bf16_launch_forms_are_bitwise_the_same(name, B):
     outs = {}
     try:
         with torch.no_grad():
-            for tag, mode in (("one", 1 << 1), ("pair", 2 << 1), ("gemm", 1), ("default", 0)):
+            for tag, mode in (("one", 1 << 1), ("gemm", 1), ("default", 0)):
                 lib.mpl_x3_stack_mode(mode | 8)
                 outs[tag] = m(P, rays=R, centers=Cn).clone()
     finally:
         lib.mpl_x3_stack_mode(0)
         m.set_matmul_precision("fp32")
     assert torch.isfinite(outs["one"]).all()
-    for tag in ("pair", "gemm", "default"):
+    for tag in ("gemm", "default"):
         assert torch.equal(outs["one"], outs[tag]), tag
 
 

@@ -367,6 +367,7 @@ def test_the_library_reports_the_form_of_a_stack_launch():
         assert form(256, 2) == cabi.FORM_TEAMS
         cabi.check(lib.mpl_x3_stack_mode(2 << 1), "stack mode")
         assert form(1024, 4) == cabi.FORM_PAIRS
+        assert form(1024, 8, parts=1) == cabi.FORM_TEAMS                                  # the two-tile stage is fp16x2 only
         cabi.check(lib.mpl_x3_stack_mode(1), "stack mode")
         assert form(1024, 4) == cabi.FORM_PER_GEMM and form(1, 2) == cabi.FORM_PER_GEMM
         cabi.check(lib.mpl_x3_stack_mode(8), "stack mode")

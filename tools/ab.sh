@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B of prebuilt library variants inside ONE gpurun call (boxes differ by a few per cent, so only same-call numbers compare):
-#   bash tools/build_variants.sh [-f file.hip] base="" x="-DH2_WT_AUX=0" ...        (here, no GPU: -> build_tmp/lib_<tag>.so)
+#   bash tools/build_variants.sh [-f file.hip] base="" x="-DH2_ABL=8" ...           (here, no GPU: -> build_tmp/lib_<tag>.so)
 #   gpurun -- 'bash tools/ab.sh "<command>" [-r rounds] base x ...'                  (on the GPU box)
 # Installs build_tmp/lib_<tag>.so as the library (the source-hash stamp stays valid, so nothing rebuilds), runs <command>,
 # prefixes every output line with the tag; `rounds` alternations (default 2).  The installed library is restored at the end.
