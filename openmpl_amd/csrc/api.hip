@@ -98,6 +98,12 @@ hipEvent_t mpl::stack_chain_event(int dev) {
 }
 
 namespace {
+std::atomic<int> g_stack_mode{(getenv("MPL_X3_LAUNCHES") != nullptr ? 1 : 0) | (getenv("MPL_NO_SMALL_STACK") != nullptr ? 8 : 0) |
+                              (getenv("MPL_WRITE_THROUGH") != nullptr ? 128 : 0)};     // mpl_x3_stack_mode: the bits at stack_mode()
+}  // namespace
+int mpl::stack_mode() { return g_stack_mode.load(); }
+
+namespace {
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
@@ -108,30 +114,35 @@ inline int earlier_device_failure() {
     return device_error_pending(dev) ? MPL_E_DEVICE : MPL_OK;
 }
 
+// bump allocator of the workspace carvers: 256-byte aligned pieces from `base` (nullptr: only the size is wanted)
+struct WsCarver {
+    char* base;
+    size_t off = 0;
+    template <class T>
+    T* take(size_t bytes) {
+        T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+        off += align_up(bytes, 256);
+        return p;
+    }
+};
+
 struct StackWs {
     float *qkv, *att, *hid, *stats;
     size_t bytes;
 };
 
 StackWs carve_stack_ws(void* base, size_t M, size_t D) {
+    WsCarver c{reinterpret_cast<char*>(base)};
     StackWs w;
-    size_t off = 0;
-    auto take = [&](size_t n_floats) {
-        float* p = base ? reinterpret_cast<float*>(reinterpret_cast<char*>(base) + off) : nullptr;
-        off += align_up(n_floats * sizeof(float), 256);
-        return p;
-    };
-    w.qkv = take(M * 3 * D);
-    w.att = take(M * D);
-    w.hid = take(M * 2 * D);
-    w.stats = take(M * 2 * (size_t)ln_stat_slices((int)D));
-    w.bytes = off;
+    w.qkv = c.take<float>(M * 3 * D * sizeof(float));
+    w.att = c.take<float>(M * D * sizeof(float));
+    w.hid = c.take<float>(M * 2 * D * sizeof(float));
+    w.stats = c.take<float>(M * 2 * (size_t)ln_stat_slices((int)D) * sizeof(float));
+    w.bytes = c.off;
     return w;
 }
 
-std::atomic<bool> g_x3_per_gemm{getenv("MPL_X3_LAUNCHES") != nullptr};
 std::atomic<int> g_spin_log2{23};    // polls before a wait inside a persistent kernel counts as lost (mpl_x3_spin_limit)
-std::atomic<int> g_x3_stop{0};   // diagnostics: stop a stack after this many GEMMs (0 = run everything)
 
 // 2 = every block carries fp16x2 operands (h2_gemm.hip, the default fp32 engine), 1 = packed bf16 operands (b1_gemm.hip), 0 = none
 // of them (or the shape has no packed layout): the stack then runs on the fp32 matrix instructions
@@ -147,62 +158,35 @@ int stack_packed_parts(const mpl_block_weights* blocks, const uint8_t* schedule,
     return np;
 }
 
-// fp16x2 path (h2_gemm.hip): x stays fp32 in place and is the A operand of the LayerNorm GEMMs; the attention output and
-// the GELU output travel as packed operands
-struct H2Ws {
-    unsigned short *att2, *hid2;
+// Workspace of the packed-operand engines.  x stays fp32 in place (residual stream, statistics); the attention output and the GELU
+// output travel as packed operands of engine np.  fp16x2 (np = 2, h2_gemm.hip): x itself is the A operand of the LayerNorm GEMMs.
+// bf16 (np = 1, b1_gemm.hip): x travels to them as the packed bf16 copy x16 that the residual epilogues rewrite.
+struct PackedWs {
+    unsigned short *x16, *att, *hid;
     float* stats;
     unsigned* counters;
     size_t bytes;
 };
-H2Ws carve_h2_ws(void* base, size_t M, size_t D, int rpt) {
-    H2Ws w;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char* p = base ? reinterpret_cast<char*>(base) + off : nullptr;
-        off += align_up(bytes, 256);
-        return p;
-    };
-    w.att2 = reinterpret_cast<unsigned short*>(take(h2_act_bytes((int)M, (int)D, rpt)));
-    w.hid2 = reinterpret_cast<unsigned short*>(take(h2_act_bytes((int)M, (int)(2 * D), rpt)));
-    w.stats = reinterpret_cast<float*>(take((M + 64) * 2 * (size_t)ln_stat_slices((int)D) * sizeof(float)));
-    w.counters = reinterpret_cast<unsigned*>(take((h2_err_index((int)((M + rpt - 1) / rpt)) + 64) * sizeof(unsigned)));
-    w.bytes = off;
+PackedWs carve_packed_ws(void* base, size_t M, size_t D, int rpt, int np) {
+    WsCarver c{reinterpret_cast<char*>(base)};
+    PackedWs w;
+    w.x16 = np == 1 ? c.take<unsigned short>(h2_act_bytes((int)M, (int)D, rpt, 1)) : nullptr;
+    w.att = c.take<unsigned short>(h2_act_bytes((int)M, (int)D, rpt, np));
+    w.hid = c.take<unsigned short>(h2_act_bytes((int)M, (int)(2 * D), rpt, np));
+    w.stats = c.take<float>((M + 64) * 2 * (size_t)ln_stat_slices((int)D) * sizeof(float));
+    w.counters = c.take<unsigned>((h2_err_index((int)((M + rpt - 1) / rpt)) + 64) * sizeof(unsigned));
+    w.bytes = c.off;
     return w;
 }
-int block_stack_h2(float* x, int n_seq, int n_tok, int D, int H, const mpl_block_weights* blocks, const uint8_t* schedule,
-                   int n_apps, void* ws, size_t ws_bytes, const unsigned** err_ws, hipStream_t s);
 
-// bf16 path (b1_gemm.hip): x stays fp32 in place (residual stream, statistics) and travels to the LayerNorm GEMMs as the packed
-// bf16 copy x16 that the residual epilogues rewrite; the attention output and the GELU output travel as packed bf16 operands
-struct B1Ws {
-    unsigned short *x16, *att1, *hid1;
-    float* stats;
-    unsigned* counters;
-    size_t bytes;
-};
-B1Ws carve_b1_ws(void* base, size_t M, size_t D, int rpt) {
-    B1Ws w;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char* p = base ? reinterpret_cast<char*>(base) + off : nullptr;
-        off += align_up(bytes, 256);
-        return p;
-    };
-    w.x16 = reinterpret_cast<unsigned short*>(take(h2_act_bytes((int)M, (int)D, rpt, 1)));
-    w.att1 = reinterpret_cast<unsigned short*>(take(h2_act_bytes((int)M, (int)D, rpt, 1)));
-    w.hid1 = reinterpret_cast<unsigned short*>(take(h2_act_bytes((int)M, (int)(2 * D), rpt, 1)));
-    w.stats = reinterpret_cast<float*>(take((M + 64) * 2 * (size_t)ln_stat_slices((int)D) * sizeof(float)));
-    w.counters = reinterpret_cast<unsigned*>(take((h2_err_index((int)((M + rpt - 1) / rpt)) + 64) * sizeof(unsigned)));
-    w.bytes = off;
-    return w;
-}
-int block_stack_b1(float* x, int n_seq, int n_tok, int D, int H, const mpl_block_weights* blocks, const uint8_t* schedule,
-                   int n_apps, void* ws, size_t ws_bytes, const unsigned** err_ws, hipStream_t s) {
+// The block stack on the packed-operand engine NP: the persistent team kernels, or one launch per GEMM (mpl_x3_stack_mode bit 0)
+template <int NP>
+int block_stack_packed(float* x, int n_seq, int n_tok, int D, int H, const mpl_block_weights* blocks, const uint8_t* schedule,
+                       int n_apps, void* ws, size_t ws_bytes, const unsigned** err_ws, hipStream_t s) {
     const int M = n_seq * n_tok, rpt = h2_rows_per_tile(n_tok);
     const float eps = 1e-6f;  // norm_layer = partial(nn.LayerNorm, eps=1e-6), multiview_mpl.py:139
     if (n_apps > MPL_MAX_APPS) return MPL_E_UNSUPPORTED;
-    const B1Ws w = carve_b1_ws(ws, (size_t)M, (size_t)D, rpt);
+    const PackedWs w = carve_packed_ws(ws, (size_t)M, (size_t)D, rpt, NP);
     if (!ws || ws_bytes < w.bytes) return MPL_E_WORKSPACE;
     const int n_tiles = (M + rpt - 1) / rpt;
     if (err_ws) *err_ws = w.counters + h2_err_index(n_tiles);
@@ -210,69 +194,43 @@ int block_stack_b1(float* x, int n_seq, int n_tok, int D, int H, const mpl_block
     const unsigned short* ops[MPL_MAX_APPS * 4];
     for (int a = 0; a < n_apps; ++a) {
         const mpl_block_weights& b = blocks[schedule[a]];
-        for (int i = 0; i < 4; ++i) ops[4 * a + i] = (&b.qkv_w16)[i];
+        for (int i = 0; i < 4; ++i) ops[4 * a + i] = NP == 2 ? (&b.qkv_h2)[i] : (&b.qkv_w16)[i];
     }
-    // entry of the stack, one launch: the rows as packed bf16 operand, their LayerNorm slice partials, zeroed counters + error word
-    if ((rc = launch_b1_entry(x, M, D, D, rpt, w.x16, w.stats, w.counters, h2_err_index(n_tiles) + 1, s))) return rc;
-    if (!g_x3_per_gemm.load(std::memory_order_relaxed))
-        return launch_b1_stack(x, w.x16, M, D, n_tok, H, ops, n_apps, w.att1, w.hid1, w.stats, w.counters, eps, g_x3_stop.load(), s);
-    // A/B switch (mpl_x3_stack_mode): the same phases as one launch per GEMM
-    const int stop = g_x3_stop.load();
-    for (int a = 0; a < n_apps; ++a) {
-        const mpl_block_weights& b = blocks[schedule[a]];
-        if ((rc = launch_b1_qkv_attention(w.x16, b.qkv_w16, w.stats, eps, M, D, n_tok, H, w.att1, s))) return rc;
-        if (stop && 4 * a + 1 >= stop) return MPL_OK;
-        if ((rc = launch_b1_gemm(w.att1, b.proj_w16, false, nullptr, 0.f, x, D, x, D, w.x16, w.stats, M, D, D, rpt, MPL_EPI_BIAS_RESIDUAL, s)))
-            return rc;
-        if (stop && 4 * a + 2 >= stop) return MPL_OK;
-        if ((rc = launch_b1_gemm(w.x16, b.fc1_w16, true, w.stats, eps, nullptr, 0, nullptr, 0, w.hid1, nullptr, M, 2 * D, D, rpt,
-                                 MPL_EPI_BIAS_GELU, s)))
-            return rc;
-        if (stop && 4 * a + 3 >= stop) return MPL_OK;
-        if ((rc = launch_b1_gemm(w.hid1, b.fc2_w16, false, nullptr, 0.f, x, D, x, D, w.x16, w.stats, M, D, 2 * D, rpt,
-                                 MPL_EPI_BIAS_RESIDUAL, s)))
-            return rc;
+    // entry of the stack, one launch: LayerNorm slice partials of the incoming rows, zeroed arrival counters + error word; fp16x2:
+    // the check that proj / fc2 were packed against the static scales of their producers (mpl_pack_h2_scaled); bf16: the rows as
+    // the packed operand x16
+    if constexpr (NP == 2) rc = launch_h2_entry(x, M, D, D, w.stats, w.counters, h2_err_index(n_tiles) + 1, ops, n_apps, s);
+    else rc = launch_b1_entry(x, M, D, D, rpt, w.x16, w.stats, w.counters, h2_err_index(n_tiles) + 1, s);
+    if (rc) return rc;
+    const int mode = g_stack_mode.load(), stop = mode >> 8;
+    if (!(mode & 1)) {
+        if constexpr (NP == 2) return launch_h2_stack(x, M, D, n_tok, H, ops, n_apps, w.att, w.hid, w.stats, w.counters, eps, stop, s);
+        else return launch_b1_stack(x, w.x16, M, D, n_tok, H, ops, n_apps, w.att, w.hid, w.stats, w.counters, eps, stop, s);
     }
-    return MPL_OK;
-}
-
-int block_stack_h2(float* x, int n_seq, int n_tok, int D, int H, const mpl_block_weights* blocks, const uint8_t* schedule,
-                   int n_apps, void* ws, size_t ws_bytes, const unsigned** err_ws, hipStream_t s) {
-    const int M = n_seq * n_tok, rpt = h2_rows_per_tile(n_tok);
-    const float eps = 1e-6f;  // norm_layer = partial(nn.LayerNorm, eps=1e-6), multiview_mpl.py:139
-    if (n_apps > MPL_MAX_APPS) return MPL_E_UNSUPPORTED;
-    const H2Ws w = carve_h2_ws(ws, (size_t)M, (size_t)D, rpt);
-    if (!ws || ws_bytes < w.bytes) return MPL_E_WORKSPACE;
-    const int n_tiles = (M + rpt - 1) / rpt;
-    if (err_ws) *err_ws = w.counters + h2_err_index(n_tiles);
-    int rc;
-    const unsigned short* ops[MPL_MAX_APPS * 4];
+    // A/B switch (mpl_x3_stack_mode bit 0): the same phases as one launch per GEMM
     for (int a = 0; a < n_apps; ++a) {
-        const mpl_block_weights& b = blocks[schedule[a]];
-        for (int i = 0; i < 4; ++i) ops[4 * a + i] = (&b.qkv_h2)[i];
-    }
-    // entry of the stack, one launch: LayerNorm slice partials of the incoming rows, zeroed arrival counters + error word, and
-    // the check that proj / fc2 were packed against the static scales of their producers (mpl_pack_h2_scaled)
-    if ((rc = launch_h2_entry(x, M, D, D, w.stats, w.counters, h2_err_index(n_tiles) + 1, ops, n_apps, s))) return rc;
-    if (!g_x3_per_gemm.load(std::memory_order_relaxed))
-        return launch_h2_stack(x, M, D, n_tok, H, ops, n_apps, w.att2, w.hid2, w.stats, w.counters, eps, g_x3_stop.load(), s);
-    // A/B switch (mpl_x3_stack_mode): the same phases as one launch per GEMM
-    const int stop = g_x3_stop.load();
-    for (int a = 0; a < n_apps; ++a) {
-        const mpl_block_weights& b = blocks[schedule[a]];
-        if ((rc = launch_h2_qkv_attention(x, b.qkv_h2, w.stats, eps, M, D, n_tok, H, w.att2, s))) return rc;
-        if (stop && 4 * a + 1 >= stop) return MPL_OK;
-        if ((rc = launch_h2_gemm(nullptr, w.att2, nullptr, b.proj_h2, false, nullptr, 0.f, x, D, x, D, nullptr, w.stats, M, D, D,
-                                 rpt, MPL_EPI_BIAS_RESIDUAL, s)))
-            return rc;
-        if (stop && 4 * a + 2 >= stop) return MPL_OK;
-        if ((rc = launch_h2_gemm(x, nullptr, nullptr, b.fc1_h2, true, w.stats, eps, nullptr, 0, nullptr, 0, w.hid2, nullptr, M, 2 * D,
-                                 D, rpt, MPL_EPI_BIAS_GELU, s)))
-            return rc;
-        if (stop && 4 * a + 3 >= stop) return MPL_OK;
-        if ((rc = launch_h2_gemm(nullptr, w.hid2, nullptr, b.fc2_h2, false, nullptr, 0.f, x, D, x, D, nullptr, w.stats, M, D,
-                                 2 * D, rpt, MPL_EPI_BIAS_RESIDUAL, s)))
-            return rc;
+        const unsigned short* const* op = ops + 4 * a;
+        if constexpr (NP == 2) rc = launch_h2_qkv_attention(x, op[0], w.stats, eps, M, D, n_tok, H, w.att, s);
+        else rc = launch_b1_qkv_attention(w.x16, op[0], w.stats, eps, M, D, n_tok, H, w.att, s);
+        if (rc) return rc;
+        for (int g = 1; g < 4; ++g) {
+            if (stop && 4 * a + g >= stop) return MPL_OK;
+            if (g == 2) {       // fc1: LayerNorm + GELU -> hid
+                if constexpr (NP == 2)
+                    rc = launch_h2_gemm(x, nullptr, nullptr, op[g], true, w.stats, eps, nullptr, 0, nullptr, 0, w.hid, nullptr, M, 2 * D, D,
+                                        rpt, MPL_EPI_BIAS_GELU, s);
+                else rc = launch_b1_gemm(w.x16, op[g], true, w.stats, eps, nullptr, 0, nullptr, 0, w.hid, nullptr, M, 2 * D, D, rpt,
+                                         MPL_EPI_BIAS_GELU, s);
+            } else {            // proj (A = att, K = D), fc2 (A = hid, K = 2 D): x += ..., its LayerNorm partials (bf16: and x16)
+                const unsigned short* A = g == 1 ? w.att : w.hid;
+                const int K = g == 1 ? D : 2 * D;
+                if constexpr (NP == 2)
+                    rc = launch_h2_gemm(nullptr, A, nullptr, op[g], false, nullptr, 0.f, x, D, x, D, nullptr, w.stats, M, D, K, rpt,
+                                        MPL_EPI_BIAS_RESIDUAL, s);
+                else rc = launch_b1_gemm(A, op[g], false, nullptr, 0.f, x, D, x, D, w.x16, w.stats, M, D, K, rpt, MPL_EPI_BIAS_RESIDUAL, s);
+            }
+            if (rc) return rc;
+        }
     }
     return MPL_OK;
 }
@@ -291,8 +249,9 @@ inline int device_cu_count(int* cus) {
 // raw = every nn.Linear / LayerNorm tensor of every scheduled block is present (the engine reads them in place); cus = compute
 // units of the device (every column tile of the widest GEMM needs a resident workgroup of its own: they poll each other's output).
 inline bool small_engine_taken(int np, bool allow_small, int M, int D, int n_tok, int H, int n_apps, int n_blocks, bool raw, int cus) {
-    return (np == 0 || np == 2) && allow_small && sm_stack_enabled() && n_apps <= MPL_MAX_APPS && raw &&
-           !g_x3_per_gemm.load(std::memory_order_relaxed) && g_x3_stop.load() == 0 && sm_stack_ok(M, D, n_tok, H, n_apps, n_blocks, cus);
+    const int mode = g_stack_mode.load();
+    return (np == 0 || np == 2) && allow_small && !((mode >> 3) & 1) && n_apps <= MPL_MAX_APPS && raw && !(mode & 1) && (mode >> 8) == 0 &&
+           sm_stack_ok(M, D, n_tok, H, n_apps, n_blocks, cus);
 }
 
 int block_stack_impl(float* x, int n_seq, int n_tok, int D, int H, const mpl_block_weights* blocks,
@@ -331,11 +290,11 @@ int block_stack_impl(float* x, int n_seq, int n_tok, int D, int H, const mpl_blo
         }
     }
     if (const int np = np0) {
-        const int rc = np == 2 ? block_stack_h2(x, n_seq, n_tok, D, H, blocks, schedule, n_apps, ws, ws_bytes, err_ws, s)
-                               : block_stack_b1(x, n_seq, n_tok, D, H, blocks, schedule, n_apps, ws, ws_bytes, err_ws, s);
+        const int rc = np == 2 ? block_stack_packed<2>(x, n_seq, n_tok, D, H, blocks, schedule, n_apps, ws, ws_bytes, err_ws, s)
+                               : block_stack_packed<1>(x, n_seq, n_tok, D, H, blocks, schedule, n_apps, ws, ws_bytes, err_ws, s);
         if (rc == MPL_OK) {
             int cus = 0;
-            t_last_form = g_x3_per_gemm.load(std::memory_order_relaxed) ? (int)MPL_FORM_PER_GEMM
+            t_last_form = (g_stack_mode.load() & 1) ? (int)MPL_FORM_PER_GEMM
                           : (device_cu_count(&cus) == MPL_OK ? h2_stack_form_code(n_seq * n_tok, D, n_tok, np, cus) : (int)MPL_E_LAUNCH);
         }
         return rc;
@@ -416,9 +375,9 @@ size_t stack_ws_bytes(size_t M, size_t D, int n_tok) {
     }
     const int rpt = h2_rows_per_tile(n_tok);
     if (rpt > 0 && n_tok <= 32 && h2_shape_ok((int)D, (int)(2 * D))) {
-        const size_t b2 = carve_h2_ws(nullptr, M, D, rpt).bytes;
+        const size_t b2 = carve_packed_ws(nullptr, M, D, rpt, 2).bytes;
         b = b2 > b ? b2 : b;
-        const size_t b1 = carve_b1_ws(nullptr, M, D, rpt).bytes;
+        const size_t b1 = carve_packed_ws(nullptr, M, D, rpt, 1).bytes;
         b = b1 > b ? b1 : b;
     }
     return b;
@@ -609,7 +568,7 @@ int mpl_block_stack_form_ex(int n_seq, int n_tok, int D, int heads, int n_apps, 
     if (M <= sm_stack_max_rows() && small_engine_taken(np, !(flags & MPL_F_NO_SMALL_STACK), M, D, n_tok, heads, n_apps, n_blocks, raw_tensors != 0, cus))
         return MPL_FORM_SMALL;
     if (np == 0) return MPL_FORM_UNPACKED;
-    if (g_x3_per_gemm.load(std::memory_order_relaxed)) return MPL_FORM_PER_GEMM;
+    if (g_stack_mode.load() & 1) return MPL_FORM_PER_GEMM;
     return h2_stack_form_code(M, D, n_tok, np, cus);
 }
 
@@ -621,13 +580,7 @@ int mpl_block_stack_form(int n_seq, int n_tok, int D, int heads, int n_apps, int
 int mpl_block_stack_last_form(void) { return t_last_form; }
 
 int mpl_x3_stack_mode(int one_launch_per_gemm) {
-    g_x3_per_gemm.store((one_launch_per_gemm & 1) != 0);
-    g_x3_stop.store(one_launch_per_gemm >> 8);
-    h2_set_write_through((one_launch_per_gemm >> 7) & 1);  // bit 7: write-through hand-off stores also for teams that sit on one XCD
-    h2_set_direct_w(((one_launch_per_gemm >> 4) & 1) ^ 1);  // bit 4: the 16-row teams in the ring form (A/B against the direct-W form)
-    h2_set_narrow((one_launch_per_gemm >> 5) & 3);         // bits 5, 6: row-narrow teams: 0 = by shape, 1 = never, 2 / 3 = 32- / 16-row workgroups where legal
-    h2_set_row_tiles((one_launch_per_gemm >> 1) & 3);      // bits 1, 2: 0 = by shape, 1 / 2 = force the one- / two-tile stage
-    sm_stack_disable((one_launch_per_gemm >> 3) & 1);      // bit 3: no small-batch engine (the team kernels for every batch)
+    g_stack_mode.store(one_launch_per_gemm);      // the bits: common.hpp stack_mode()
     return MPL_OK;
 }
 

@@ -169,22 +169,6 @@ int launch_b1_entry(const float* X, int M, int K, int ldx, int rpt, unsigned sho
     return hip_check_launch();
 }
 
-// ---------------------------------------------------------------------------------------------- launches
-template <int EPI, bool LNF, int NPASS>
-static int launch_b1(const H2Args& a, hipStream_t s) {
-    static std::atomic<bool> attr_set[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return MPL_E_LAUNCH;
-    if (!attr_set[dev].load(std::memory_order_acquire)) {
-        if (hipFuncSetAttribute((const void*)h2_gemm_kernel<EPI, LNF, NPASS, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, H2_LDS_BYTES) != hipSuccess)
-            return MPL_E_LAUNCH;
-        attr_set[dev].store(true, std::memory_order_release);
-    }
-    ProfScope prof(MPL_K_GEMM, s);
-    hipLaunchKernelGGL((h2_gemm_kernel<EPI, LNF, NPASS, 1>), dim3(a.grid_m * a.grid_n), dim3(512), H2_LDS_BYTES, s, a);
-    return hip_check_launch();
-}
-
 // One GEMM of a block application as a launch of its own (mpl_x3_stack_mode(1): the A/B form of the stack): fc1 (ln, GELU, two
 // column groups per workgroup) or proj / fc2 (residual; C = the fp32 rows, C1 = their packed copy, stats_out = their partials)
 int launch_b1_gemm(const unsigned short* A1, const unsigned short* W1, bool ln, const float* stats, float eps, const float* R, int ldr,
@@ -197,9 +181,9 @@ int launch_b1_gemm(const unsigned short* A1, const unsigned short* W1, bool ln, 
              stats_out, M, N, K, rpt, (M + rpt - 1) / rpt, N / BN, eps, 0, 0, h2_debug_buffer(), nullptr, nullptr, 0};
     if (epi == MPL_EPI_BIAS_GELU && ln && (a.grid_n & 1) == 0 && C1 && !C) {
         a.grid_n /= 2;
-        return launch_b1<H2_EPI_GELU, true, 2>(a, s);
+        return launch_h2<H2_EPI_GELU, true, 2, 1>(a, s);
     }
-    if (epi == MPL_EPI_BIAS_RESIDUAL && !ln && R && C) return launch_b1<H2_EPI_RES, false, 1>(a, s);
+    if (epi == MPL_EPI_BIAS_RESIDUAL && !ln && R && C) return launch_h2<H2_EPI_RES, false, 1, 1>(a, s);
     return MPL_E_UNSUPPORTED;
 }
 
@@ -213,7 +197,7 @@ int launch_b1_qkv_attention(const unsigned short* x16, const unsigned short* W1,
     H2Args a{reinterpret_cast<const char*>(x16), nullptr, 0, w1, vec, vec + N, stats, nullptr, nullptr, nullptr, 0, nullptr, 0,
              reinterpret_cast<char*>(att1), nullptr, M, N, D, rpt, (M + rpt - 1) / rpt, D / BN, eps, n_tok, D / heads, h2_debug_buffer(),
              nullptr, nullptr, 0};
-    return launch_b1<H2_EPI_ATT, true, 3>(a, s);
+    return launch_h2<H2_EPI_ATT, true, 3, 1>(a, s);
 }
 
 int launch_b1_stack(float* x, unsigned short* x16, int M, int D, int n_tok, int heads, const unsigned short* const* ops, int n_apps,

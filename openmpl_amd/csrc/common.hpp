@@ -147,6 +147,23 @@ inline int hip_check_launch() {
     return e == hipSuccess ? MPL_OK : MPL_E_LAUNCH;
 }
 
+// Opt KERNEL into `lds` bytes of dynamic LDS (> 64 KiB needs it), once per (kernel, device).  threads > 0: also require that a
+// workgroup of `threads` threads with that LDS fits a compute unit at all (MPL_E_UNSUPPORTED otherwise).
+template <auto KERNEL>
+int kernel_lds_once(int lds, int threads = 0) {
+    static std::atomic<bool> done[64];   // set-once flags: a racing second hipFuncSetAttribute is harmless
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return MPL_E_LAUNCH;
+    if (done[dev].load(std::memory_order_acquire)) return MPL_OK;
+    const void* k = reinterpret_cast<const void*>(KERNEL);
+    if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return MPL_E_LAUNCH;
+    int per_cu = 0;
+    if (threads > 0 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, threads, lds) != hipSuccess || per_cu < 1))
+        return MPL_E_UNSUPPORTED;
+    done[dev].store(true, std::memory_order_release);
+    return MPL_OK;
+}
+
 // ---- kernel launchers (defined in the .hip files) -------------------------------------------
 // LayerNorm statistics buffer: 2 * M * ln_stat_slices(K) floats (per-slice {mean, M2}, see ln_gemm.hip)
 inline int ln_stat_slices(int K) { return (K % 136 == 0) ? K / 136 : 1; }
@@ -175,15 +192,21 @@ int take_fault_injection();
 // streams would then depend on a graph-internal node) and a graph replay would bypass altogether
 int refuse_stream_capture(hipStream_t s);
 void h2_set_spin_log2(int log2_polls);     // test hook (mpl_x3_spin_limit)
-void h2_set_row_tiles(int rt);             // A/B switch of the block stack: 0 by shape, 1 / 2 row tiles per stage
-void h2_set_narrow(int mode);              // row-narrow teams: 0 by shape, 1 never, 2 / 3 = 32- / 16-row workgroups where legal
+// The A/B switches of the block stack (mpl_x3_stack_mode): ONE word (api.hip), decoded where it is read.
+//   bit 0      one launch per GEMM instead of the persistent kernels (block_stack_impl, small_engine_taken)
+//   bits 1, 2  0 = by shape, 1 / 2 = force the one- / two-tile stage (h2_stack_form)
+//   bit 3      no small-batch engine: the team kernels for every batch (small_engine_taken)
+//   bit 4      the 16-row teams in the ring form instead of the direct-W form (h2_stack_form)
+//   bits 5, 6  row-narrow teams: 0 = by shape, 1 = never, 2 / 3 = 32- / 16-row workgroups where legal (h2_stack_form)
+//   bit 7      write-through hand-off stores also for teams that sit on one XCD (h2_launch_stack)
+//   bits 8..   diagnostics: stop a stack after this many GEMMs, 0 = run everything (block_stack_impl, small_engine_taken)
+// At start-up: bit 0 = MPL_X3_LAUNCHES, bit 3 = MPL_NO_SMALL_STACK, bit 7 = MPL_WRITE_THROUGH (set in the environment).
+int stack_mode();
 // arrival counters of a stack call: one per (row tile, 16-row group) -- the row-narrow teams synchronise per sub-tile -- then the error word
 constexpr int H2_CTR_PER_TILE = 4;
 constexpr int H2_XCC_WORDS = 256;          // behind the arrival counters: one word per team, the set of XCDs its workgroups run on
 inline int h2_err_index(int n_tiles) { return H2_CTR_PER_TILE * n_tiles + H2_XCC_WORDS; }      // the error word of the call (the last word)
 int h2_stack_form_code(int M, int D, int n_tok, int np, int cus);      // h2_gemm.hip: MPL_FORM_* of a team launch of this shape
-void h2_set_direct_w(int on);              // A/B switch: 0 = the 16-row teams run the ring form (h2n_gemm.hip) instead of the direct-W form
-void h2_set_write_through(int always);     // A/B switch: 1 = write-through hand-off stores whatever the placement of a team
 // The persistent block-stack kernels (h2_stack_kernel and its pair forms, sm_stack_kernel) need every workgroup resident: the library
 // serialises its own launches of them per device, whatever stream they are on -- each launch waits for the event recorded
 // behind the previous one (api.hip).  The event exists from the first call (waiting on a never-recorded event is a no-op).
@@ -230,8 +253,6 @@ int launch_b1_stack(float* x, unsigned short* x16, int M, int D, int n_tok, int 
 // Block stack for up to 80 token rows (sm_stack.hip; beyond one sequence: groups of sequences of at most 16 rows side by side): every GEMM on the whole chip (one 16-column tile per workgroup, weights
 // read in place), activations handed over as {value, tag} pairs, exact fp32 on the matrix cores
 bool sm_stack_ok(int M, int D, int n_tok, int H, int n_apps, int n_blocks, int cus);      // cus: every workgroup must be resident
-bool sm_stack_enabled();
-void sm_stack_disable(int off);            // A/B switch (mpl_x3_stack_mode bit 3)
 size_t sm_stack_ws_bytes(int M, int D);
 int sm_stack_max_rows();
 int launch_sm_stack(float* x, int n_seq, int n_tok, int D, int H, const mpl_block_weights* blocks, const uint8_t* schedule, int n_apps,

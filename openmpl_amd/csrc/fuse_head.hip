@@ -45,18 +45,11 @@ int launch_fuse_head(const mpl_config* cfg, const mpl_weights* w, const float* x
                      const unsigned* err_ws, hipStream_t s) {
     FhParams p;
     if (batch <= 0 || !fh_params(cfg, w, &p)) return MPL_E_UNSUPPORTED;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return MPL_E_LAUNCH;
     constexpr int poses = 4;
     constexpr int LDS = (FH_W_FLOATS + poses * kMaxE) * 4;
-    void (*kernel)(const float*, int, const FhParams, float*, float*, const unsigned*) = fuse_head_kernel<poses>;
-    static std::atomic<bool> attr_set[64];   // set-once flags: a racing second hipFuncSetAttribute is harmless
-    if (!attr_set[dev].load(std::memory_order_acquire)) {
-        if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) return MPL_E_LAUNCH;
-        attr_set[dev].store(true, std::memory_order_release);
-    }
+    if (int rc = kernel_lds_once<fuse_head_kernel<poses>>(LDS)) return rc;
     ProfScope prof(MPL_K_FUSE_HEAD, s);
-    hipLaunchKernelGGL(kernel, dim3((batch + poses - 1) / poses), dim3(64 * poses), LDS, s, x, batch, p, out, y_out, err_ws);
+    hipLaunchKernelGGL(fuse_head_kernel<poses>, dim3((batch + poses - 1) / poses), dim3(64 * poses), LDS, s, x, batch, p, out, y_out, err_ws);
     return hip_check_launch();
 }
 

@@ -357,39 +357,9 @@ int launch_h2_pack_rows(const float* X, int M, int K, int ldx, int rpt, unsigned
 static std::atomic<unsigned long long*> g_h2_dbg{nullptr};
 void h2_set_debug_buffer(unsigned long long* p) { g_h2_dbg.store(p); }
 static std::atomic<int> g_h2_spin_log2{23};
-static std::atomic<int> g_h2_rt{0};          // 0: by shape; 1 / 2: force the one- / two-tile stage (A/B switch)
-void h2_set_row_tiles(int rt) { g_h2_rt.store(rt); }
 void h2_set_spin_log2(int v) { g_h2_spin_log2.store(v & 0xff); }
 unsigned long long* h2_debug_buffer() { return g_h2_dbg.load(); }
 int h2_spin_log2() { return g_h2_spin_log2.load(); }
-int h2_row_tiles() { return g_h2_rt.load(); }
-static std::atomic<int> g_h2_narrow{0};
-void h2_set_narrow(int mode) { g_h2_narrow.store(mode & 3); }
-int h2_narrow_mode() { return g_h2_narrow.load(); }
-static std::atomic<int> g_h2_wt_always{getenv("MPL_WRITE_THROUGH") != nullptr ? 1 : 0};
-void h2_set_write_through(int always) { g_h2_wt_always.store(always & 1); }
-int h2_write_through_always() { return g_h2_wt_always.load(); }
-static std::atomic<int> g_h2_direct_w{1};
-void h2_set_direct_w(int on) { g_h2_direct_w.store(on & 1); }
-int h2_direct_w() { return g_h2_direct_w.load(); }
-
-
-template <int EPI, bool LNF, int NPASS>
-static int launch_h2(const H2Args& a, hipStream_t s) {
-    constexpr int LDS = H2_LDS_BYTES;
-    static_assert(LDS <= 160 * 1024, "LDS ring too large");
-    static std::atomic<bool> attr_set[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return MPL_E_LAUNCH;
-    if (!attr_set[dev].load(std::memory_order_acquire)) {
-        if (hipFuncSetAttribute((const void*)h2_gemm_kernel<EPI, LNF, NPASS>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess)
-            return MPL_E_LAUNCH;
-        attr_set[dev].store(true, std::memory_order_release);
-    }
-    ProfScope prof(MPL_K_GEMM, s);
-    hipLaunchKernelGGL((h2_gemm_kernel<EPI, LNF, NPASS>), dim3(a.grid_m * a.grid_n), dim3(512), LDS, s, a);
-    return hip_check_launch();
-}
 
 // One GEMM as a launch of its own.  ln: A = fp32 rows X (ld = K) normalised with `stats`; else A = packed A2 whose scale
 // reciprocal sits at a_inv (device; NULL = the operand carries the per-column static scales W2 was packed against).

@@ -1862,16 +1862,21 @@ __global__ __launch_bounds__(512, 2) void h2_stackd_kernel(const H2StackArgs s) 
     }
 }
 
-// ---------------------------------------------------------------------------------------------- host side of the stack launch
-unsigned long long* h2_debug_buffer();       // h2_gemm.hip (A/B switches and test hooks shared by both engines)
+// ---------------------------------------------------------------------------------------------- host side
+unsigned long long* h2_debug_buffer();       // h2_gemm.hip (test hooks shared by both engines)
 int h2_spin_log2();
-int h2_row_tiles();
-int h2_narrow_mode();
-int h2_write_through_always();
-int h2_direct_w();
-struct H2StackArgs;
 int launch_h2n_stack(const H2StackArgs& a, int grid, hipStream_t s);      // h2n_gemm.hip: the row-narrow stack kernel
 int launch_h2d_stack(const H2StackArgs& a, int grid, hipStream_t s);      // h2d_gemm.hip: its direct-W form for 16-row teams
+
+// One GEMM of engine NP as a launch of its own (the unit-test entries and the per-GEMM form of the stack)
+template <int EPI, bool LNF, int NPASS, int NP = 2>
+static int launch_h2(const H2Args& a, hipStream_t s) {
+    static_assert(H2_LDS_BYTES <= 160 * 1024, "LDS ring too large");
+    if (int rc = kernel_lds_once<h2_gemm_kernel<EPI, LNF, NPASS, NP>>(H2_LDS_BYTES)) return rc;
+    ProfScope prof(MPL_K_GEMM, s);
+    hipLaunchKernelGGL((h2_gemm_kernel<EPI, LNF, NPASS, NP>), dim3(a.grid_m * a.grid_n), dim3(512), H2_LDS_BYTES, s, a);
+    return hip_check_launch();
+}
 
 // THE rule by which a stack launch picks its kernel form, in one place: h2_launch_stack follows it and mpl_block_stack_form
 // (api.hip) reports it (bench.py names the kernel after it, tests pin it).  By the shape of the launch, the device and the A/B
@@ -1887,15 +1892,16 @@ static H2Form h2_stack_form(int M, int D, int n_tok, int cus) {
     const int rpt = h2_rows_per_tile(n_tok), n_tiles = (M + rpt - 1) / rpt, G = D / BN;
     const int cap = cus / G;
     // more row tiles than teams the chip holds (fp16x2 operands): teams walk PAIRS of row tiles with the two-tile stage.
-    // h2_row_tiles(): A/B switch (mpl_x3_stack_mode bits 1, 2).  bf16 operands (NP = 1) always go one tile at a time (a pair
+    // force: A/B switch (mpl_x3_stack_mode bits 1, 2).  bf16 operands (NP = 1) always go one tile at a time (a pair
     // form of every phase was measured in round 5 and was slower, HISTORY.md)
-    const int force = h2_row_tiles();
+    const int mode = stack_mode();
+    const int force = (mode >> 1) & 3;
     f.pairs = (NP == 2 && (force == 2 || (force == 0 && n_tiles > cap))) ? 1 : 0;
     // row-narrow teams (fp16x2 operands): when whole-tile teams would leave compute units idle, a tile is split into sub-tiles of
     // 16 or 32 rows -- the narrowest form that still gives every workgroup a compute unit of its own.  Sequences must not straddle
     // row groups: 16 a multiple of n_tok
     if (NP == 2 && !f.pairs && rpt == BM && (16 % n_tok) == 0) {
-        const int nm = h2_narrow_mode();
+        const int nm = (mode >> 5) & 3;
         if (nm == 3) f.rgs = 1;
         else if (nm == 2) f.rgs = 2;
         else if (nm == 0 && force == 0) {
@@ -1905,7 +1911,7 @@ static H2Form h2_stack_form(int M, int D, int n_tok, int cus) {
     }
     // 16-row teams: the direct-W form while the A operand of the widest GEMM (fc2, K = 2 D: 2 KiB per k-tile) fits below the
     // statistics rows in LDS (mpl_x3_stack_mode bit 4: the ring form, for A/B)
-    f.direct = (f.rgs == 1 && h2_direct_w() && h2_ksteps(2 * D, 2) * 2048 <= 72 * 1024) ? 1 : 0;
+    f.direct = (f.rgs == 1 && !((mode >> 4) & 1) && h2_ksteps(2 * D, 2) * 2048 <= 72 * 1024) ? 1 : 0;
     return f;
 }
 
@@ -1919,22 +1925,17 @@ static int h2_launch_stack(float* x, unsigned short* x16, int M, int D, int n_to
     if (!x || !ops || !att2 || !hid2 || !stats || !counters || M <= 0 || n_apps <= 0 || n_apps > MPL_MAX_APPS ||
         !h2_attention_fusable(n_tok, D, heads) || !h2_shape_ok(D, 2 * D) || M % n_tok)
         return MPL_E_INVALID;
-    static std::atomic<int> resident[64];
+    if (int rc = kernel_lds_once<h2_stack_kernel<NP>>(H2_LDS_BYTES, 512)) return rc;
+    if constexpr (NP == 2) {
+        if (int rc = kernel_lds_once<h2_stack2_kernel<2>>(H2_LDS_BYTES, 512)) return rc;
+    }
+    static std::atomic<int> n_cus[64];
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return MPL_E_LAUNCH;
-    if (!resident[dev].load(std::memory_order_acquire)) {
-        int cus = 0, per_cu = 0;
+    int cus = n_cus[dev].load(std::memory_order_acquire);
+    if (cus == 0) {
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) return MPL_E_LAUNCH;
-        if (hipFuncSetAttribute((const void*)h2_stack_kernel<NP>, hipFuncAttributeMaxDynamicSharedMemorySize, H2_LDS_BYTES) != hipSuccess)
-            return MPL_E_LAUNCH;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)h2_stack_kernel<NP>, 512, H2_LDS_BYTES) != hipSuccess || per_cu < 1)
-            return MPL_E_UNSUPPORTED;
-        if constexpr (NP == 2) {
-            const void* pk = (const void*)h2_stack2_kernel<2>;
-            if (hipFuncSetAttribute(pk, hipFuncAttributeMaxDynamicSharedMemorySize, H2_LDS_BYTES) != hipSuccess) return MPL_E_LAUNCH;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pk, 512, H2_LDS_BYTES) != hipSuccess || per_cu < 1) return MPL_E_UNSUPPORTED;
-        }
-        resident[dev].store(cus, std::memory_order_release);
+        n_cus[dev].store(cus, std::memory_order_release);
     }
     H2StackArgs a;
     a.att2 = reinterpret_cast<char*>(att2);
@@ -1947,9 +1948,9 @@ static int h2_launch_stack(float* x, unsigned short* x16, int M, int D, int n_to
     a.rpt = h2_rows_per_tile(n_tok);
     a.n_tiles = (M + a.rpt - 1) / a.rpt;
     a.G = D / BN;
-    const int cap = resident[dev].load() / a.G;
+    const int cap = cus / a.G;
     if (cap < 1) return MPL_E_UNSUPPORTED;
-    const H2Form form = h2_stack_form<NP>(M, D, n_tok, resident[dev].load());
+    const H2Form form = h2_stack_form<NP>(M, D, n_tok, cus);
     const bool pairs = form.pairs != 0;
     const int n_units = pairs ? (a.n_tiles + 1) / 2 : a.n_tiles;
     a.rgs = form.rgs;
@@ -1957,14 +1958,14 @@ static int h2_launch_stack(float* x, unsigned short* x16, int M, int D, int n_to
     // (tools/wt_ab.py): bf16 engine -2 .. -4 % stack time (its stage is bound by the L2 -> LDS path, half of its bytes are
     // activations), row-narrow teams -2 %, headline fp16x2 stack 0 % in time but 9 % less fabric traffic (2.43 -> 2.22 GB per
     // launch, L2 hit rate 80 -> 89 %: profiles/r05_gemm_traffic.json); FULL on the two-tile stage +1.7 % (slower): write-through there
-    a.plain_ok = (!h2_write_through_always() && !pairs) ? 1 : 0;
+    a.plain_ok = (!((stack_mode() >> 7) & 1) && !pairs) ? 1 : 0;
     const int n_units_n = a.rgs == 4 ? n_units : a.n_tiles * (4 / a.rgs);
     a.n_teams = n_units_n < cap ? n_units_n : cap;
     if (a.n_teams * a.G > H2_MAX_WGS) a.n_teams = H2_MAX_WGS / a.G;
     // residency: every workgroup that takes part (n_teams x G <= cap x G <= CUs) needs a CU of its own -- 160 KiB of LDS make that
     // ONE per CU whatever the occupancy API reports (it is only asked whether the kernel fits at all); the grid is rounded up to
     // whole XCD rounds, the surplus blocks leave at once (team >= n_teams)
-    if (a.n_teams * a.G > resident[dev].load()) return MPL_E_UNSUPPORTED;
+    if (a.n_teams * a.G > cus) return MPL_E_UNSUPPORTED;
     a.n_apps = n_apps;
     a.n_phases = (stop_after > 0 && stop_after < 4 * n_apps) ? stop_after : 4 * n_apps;
     a.eps = eps;

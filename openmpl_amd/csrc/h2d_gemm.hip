@@ -9,17 +9,7 @@
 namespace mpl {
 
 int launch_h2d_stack(const H2StackArgs& a, int grid, hipStream_t s) {
-    static std::atomic<bool> ready[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return MPL_E_LAUNCH;
-    if (!ready[dev].load(std::memory_order_acquire)) {
-        int per_cu = 0;
-        if (hipFuncSetAttribute((const void*)h2_stackd_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, H2_LDS_BYTES) != hipSuccess)
-            return MPL_E_LAUNCH;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)h2_stackd_kernel<2>, 512, H2_LDS_BYTES) != hipSuccess || per_cu < 1)
-            return MPL_E_UNSUPPORTED;
-        ready[dev].store(true, std::memory_order_release);
-    }
+    if (int rc = kernel_lds_once<h2_stackd_kernel<2>>(H2_LDS_BYTES, 512)) return rc;
     if (a.rgs != 1) return MPL_E_INVALID;
     hipLaunchKernelGGL(h2_stackd_kernel<2>, dim3(grid), dim3(512), H2_LDS_BYTES, s, a);
     return MPL_OK;

@@ -358,15 +358,7 @@ static int launch_ng(const float* A, int lda, const float* stats, const float* l
     static_assert(LDS <= 160 * 1024, "LDS ring too large");
     const int gm = (M + BM - 1) / BM, gn = (N + BN * NG - 1) / (BN * NG);
     static_assert(!ATT || (BM * (3 * BN + 4) + ATT_SCORE_FLOATS) * 4 <= LDS, "attention epilogue does not fit in the ring");
-    static std::atomic<bool> attr_set[64];   // set-once flags: a racing second hipFuncSetAttribute is harmless
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return MPL_E_LAUNCH;
-    if (!attr_set[dev].load(std::memory_order_acquire)) {
-        if (hipFuncSetAttribute((const void*)ln_gemm_ng_kernel<EPI, LN, NG, NST, ATT>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess)
-            return MPL_E_LAUNCH;
-        attr_set[dev].store(true, std::memory_order_release);
-    }
+    if (int rc = kernel_lds_once<ln_gemm_ng_kernel<EPI, LN, NG, NST, ATT>>(LDS)) return rc;
     ProfScope prof(MPL_K_GEMM, s);
     hipLaunchKernelGGL((ln_gemm_ng_kernel<EPI, LN, NG, NST, ATT>), dim3(gm * gn), dim3(256 * NG), LDS, s,
                        A, lda, stats, ln_w, ln_b, W, bias, R, ldr, C, ldc, M, N, K, gm, gn, eps, stats_out, att_ntok,
@@ -595,15 +587,7 @@ static int launch_cs(const float* A, int lda, const float* stats, const float* l
     constexpr int LDS = CS_NST * SubStage<1>::BYTES + CS_XFER;
     static_assert(LDS <= 160 * 1024, "LDS ring too large");
     const int gm = (M + BM - 1) / BM, gn = (N + BN - 1) / BN;
-    static std::atomic<bool> attr_set[64];   // set-once flags: a racing second hipFuncSetAttribute is harmless
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return MPL_E_LAUNCH;
-    if (!attr_set[dev].load(std::memory_order_acquire)) {
-        if (hipFuncSetAttribute((const void*)ln_gemm_cs_kernel<EPI, LN>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                LDS) != hipSuccess)
-            return MPL_E_LAUNCH;
-        attr_set[dev].store(true, std::memory_order_release);
-    }
+    if (int rc = kernel_lds_once<ln_gemm_cs_kernel<EPI, LN>>(LDS)) return rc;
     ProfScope prof(MPL_K_GEMM, s);
     hipLaunchKernelGGL((ln_gemm_cs_kernel<EPI, LN>), dim3(gm * gn), dim3(576), LDS, s, A, lda, stats, ln_w, ln_b, W,
                        bias, R, ldr, C, ldc, M, N, K, gm, gn, eps, stats_out);

@@ -577,9 +577,6 @@ __global__ __launch_bounds__(SM_NT) void sm_stack_kernel(const SmArgs a) {
 #ifdef SM_DBG
 extern "C" int mpl_sm_dbg(void* out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(sm_dbg_buf), sizeof(sm_dbg_buf)); }
 #endif
-static std::atomic<int> g_sm_off{getenv("MPL_NO_SMALL_STACK") != nullptr ? 1 : 0};
-void sm_stack_disable(int off) { g_sm_off.store(off); }
-bool sm_stack_enabled() { return g_sm_off.load() == 0; }
 
 // blocks: HOST array; schedule[a] indexes it.  ws: sm_stack_ws_bytes(M, D) bytes; *err_ws receives the error word of this call.
 int launch_sm_stack(float* x, int n_seq, int n_tok, int D, int H, const mpl_block_weights* blocks, const uint8_t* schedule, int n_apps,
@@ -623,20 +620,11 @@ int launch_sm_stack(float* x, int n_seq, int n_tok, int D, int H, const mpl_bloc
     }
     if (err_ws) *err_ws = a.err_ws;
     if (int rc = refuse_stream_capture(s)) return rc;
-    void (*kernel)(const SmArgs) = sm_stack_kernel;
-    static std::atomic<bool> attr_set[64];
-    if (!attr_set[dev].load(std::memory_order_acquire)) {
-        if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SM_LDS_BYTES) != hipSuccess)
-            return MPL_E_LAUNCH;
-        // workgroups that poll each other's output need grid <= resident workgroups.  The LDS footprint (~150 KiB of 160) allows ONE workgroup per CU
-        // whatever the occupancy API says, so the API's known over-count of one block per CU at 81 .. 112 SGPRs (256-thread
-        // blocks, MI355X_MICROARCH.md "Correctness boundaries"; these kernels spill ~340 SGPRs and sit in that bucket) cannot
-        // strand a workgroup here: per_cu is clamped to 1 and the grid (<= cus, checked above) to per_cu x CUs
-        int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kernel, SM_NT, SM_LDS_BYTES) != hipSuccess || per_cu < 1)
-            return MPL_E_UNSUPPORTED;
-        attr_set[dev].store(true, std::memory_order_release);
-    }
+    // workgroups that poll each other's output need grid <= resident workgroups.  The LDS footprint (~150 KiB of 160) allows ONE workgroup per CU
+    // whatever the occupancy API says, so the API's known over-count of one block per CU at 81 .. 112 SGPRs (256-thread
+    // blocks, MI355X_MICROARCH.md "Correctness boundaries"; these kernels spill ~340 SGPRs and sit in that bucket) cannot
+    // strand a workgroup here: per_cu is clamped to 1 and the grid (<= cus, checked above) to per_cu x CUs
+    if (int rc = kernel_lds_once<sm_stack_kernel>(SM_LDS_BYTES, SM_NT)) return rc;
     // tag 0 = "not of this launch": the pairs of an earlier launch on this workspace carry the same step numbers
     if (hipMemsetAsync(ws, 0, ((size_t)M * 14 * D + SM_TAIL_WORDS) * sizeof(float), s) != hipSuccess) return MPL_E_LAUNCH;
     // workgroups that wait for each other need the chip like the team kernels do: serialised with them per device (api.hip)
@@ -647,7 +635,7 @@ int launch_sm_stack(float* x, int n_seq, int n_tok, int D, int H, const mpl_bloc
     int rc;
     {
         ProfScope prof(MPL_K_GEMM, s);
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(SM_NT), SM_LDS_BYTES, s, a);
+        hipLaunchKernelGGL(sm_stack_kernel, dim3(grid), dim3(SM_NT), SM_LDS_BYTES, s, a);
         rc = hip_check_launch();
     }
     if (hipEventRecord(ev, s) != hipSuccess) return MPL_E_LAUNCH;

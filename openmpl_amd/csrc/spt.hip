@@ -1393,15 +1393,10 @@ int launch_spt(const mpl_config* cfg, const mpl_weights* w, const mpl_inputs* in
     }
     p.n_apps = n;
     // >64 KiB of dynamic LDS needs an explicit opt-in, once per device
-    static std::atomic<bool> attr_set[64];   // set-once flags: a racing second hipFuncSetAttribute is harmless
+    if (int rc = kernel_lds_once<spt_kernel<false>>(SPT_LDS_BYTES)) return rc;
+    if (int rc = kernel_lds_once<spt_kernel<true>>(SPT_SMALL_LDS_BYTES)) return rc;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return MPL_E_LAUNCH;
-    if (!attr_set[dev].load(std::memory_order_acquire)) {
-        if (hipFuncSetAttribute((const void*)spt_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, SPT_LDS_BYTES) != hipSuccess ||
-            hipFuncSetAttribute((const void*)spt_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, SPT_SMALL_LDS_BYTES) != hipSuccess)
-            return MPL_E_LAUNCH;
-        attr_set[dev].store(true, std::memory_order_release);
-    }
     // Sequences per workgroup of the fp32-MFMA kernel: as few as keep the launch inside one wave of workgroups (one per CU), so
     // that a single frame or a few hundred sequences use the whole chip with 2-3 live row tiles per workgroup instead of a few
     // workgroups with 17; up to SPT_SMALL_SPW per workgroup run the staged form (spt_kernel<true>).
@@ -1422,13 +1417,10 @@ int launch_spt(const mpl_config* cfg, const mpl_weights* w, const mpl_inputs* in
     ProfScope prof(MPL_K_SPT, s);
     if (use_packed) {
         void (*k3)(const SptParams) = ss == 1 ? spt3_kernel<1> : ss == 2 ? spt3_kernel<2> : ss == 4 ? spt3_kernel<4> : ss == 8 ? spt3_kernel<8> : spt3_kernel<16>;
-        const int ki = ss == 1 ? 0 : ss == 2 ? 1 : ss == 4 ? 2 : ss == 8 ? 3 : 4;
-        static std::atomic<bool> attr3[64][5];
-        if (!attr3[dev][ki].load(std::memory_order_acquire)) {
-            if (hipFuncSetAttribute((const void*)k3, hipFuncAttributeMaxDynamicSharedMemorySize, SPT3_LDS_BYTES) != hipSuccess)
-                return MPL_E_LAUNCH;
-            attr3[dev][ki].store(true, std::memory_order_release);
-        }
+        const int rc = ss == 1 ? kernel_lds_once<spt3_kernel<1>>(SPT3_LDS_BYTES) : ss == 2 ? kernel_lds_once<spt3_kernel<2>>(SPT3_LDS_BYTES)
+                     : ss == 4 ? kernel_lds_once<spt3_kernel<4>>(SPT3_LDS_BYTES) : ss == 8 ? kernel_lds_once<spt3_kernel<8>>(SPT3_LDS_BYTES)
+                     : kernel_lds_once<spt3_kernel<16>>(SPT3_LDS_BYTES);
+        if (rc) return rc;
         hipLaunchKernelGGL(k3, dim3(grid), dim3(NTHR), SPT3_LDS_BYTES, s, p);
     } else {
         if (p.spw <= SPT_SMALL_SPW) hipLaunchKernelGGL(spt_kernel<true>, dim3(grid), dim3(NTHR), SPT_SMALL_LDS_BYTES, s, p);
