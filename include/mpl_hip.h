@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define MPL_HIP_ABI_VERSION 13
+#define MPL_HIP_ABI_VERSION 14
 #define MPL_MAX_VIEWS 32
 #define MPL_MAX_APPS 64 /* max Block applications in one stack schedule */
 
@@ -66,6 +66,9 @@ extern "C" {
  * team kernels (fp16x2 operands): two fp32 engines that agree to ~1e-7 but not bit for bit.  With this flag the team kernels
  * run for EVERY batch size, so that a pose carries the same bits whatever batch or shard it arrives in. */
 #define MPL_F_NO_SMALL_STACK (1u << 12)
+/* not a constructor kwarg: run the SPT stage on the shape-general kernel (csrc/spt_any.hip: any J / d / H, fp32 FMA on the
+ * nn.Linear tensors) also at J = 17, d = 32, H = 8, where the tuned kernels normally run.  Every other shape takes it anyway. */
+#define MPL_F_GENERIC_SPT (1u << 13)
 
 /* epilogues of mpl_ln_linear */
 #define MPL_EPI_BIAS 0          /* y = a W^T + b                       (attn.qkv) */
@@ -152,6 +155,16 @@ typedef struct mpl_inputs {
 
 int mpl_hip_abi_version(void);
 const char *mpl_hip_error_string(int code);
+
+/* The supported envelope, decided here and nowhere else: MPL_OK or MPL_E_UNSUPPORTED (MPL_E_INVALID for a NULL cfg).
+ * mpl_forward and mpl_spt_tokens refuse anything outside it before they launch.
+ *   1 <= num_joints <= 64;  1 <= dim <= 128;  heads >= 1 with dim % heads == 0 (the reference fails in the qkv reshape otherwise);
+ *   FPT width J*d (x2 with MPL_F_RAYS_TOKEN) <= 4096;  1 <= num_views <= MPL_MAX_VIEWS;  depth 0..60 (0..31 with
+ *   MPL_F_CONF_ATTN_W: every SPT block then runs twice);
+ *   MPL_F_POS3D_TO_RAYS only with MPL_F_RAYS_TOKEN and not with MPL_F_POS3D_SPATIAL (the reference fails, :483);
+ *   MPL_F_KPTOK (FPT blocks over J*V tokens of width d): not with MPL_F_RAYS_TOKEN; up to 32 tokens any head dim, more tokens
+ *   need head dim 4 or 8 and J*V*hd*8 <= 64 KiB (K / V of one head resident in LDS). */
+int mpl_config_supported(const mpl_config *cfg);
 
 /* FPT token width D_f = J*d (x2 with MPL_F_RAYS_TOKEN), multiview_mpl.py:140-142. */
 int mpl_fpt_width(const mpl_config *cfg);
@@ -257,7 +270,8 @@ int mpl_block_stack_last_form(void);
 int mpl_token_attention(const float *qkv, int n_seq, int n_tok, int dim, int heads, float *out, void *stream);
 
 /* Stage 3: strip ray features, View_norm, Conv1d weighted mean over views, head LN + Linear.
- * x (B*V, D_f) -> out (B, 3J).  forward_features :425-446, head :521-523. */
+ * x (B*V, D_f) -> out (B, 3J).  forward_features :425-446, head :521-523.  Any E = J*d up to 4096 (J*d <= 544 and
+ * 3J * J*d <= 28 K: the fused LDS form; beyond it a shape-general kernel, one workgroup per pose). */
 int mpl_fuse_head(const mpl_config *cfg, const mpl_weights *w, const float *x, int batch, float *out, void *stream);
 
 /* ---- output-side variants (constructor flags linear_weighted_mean, deep_head, head_kadkhod; :277-317, :506-519).
@@ -301,12 +315,13 @@ int mpl_prepare_inputs(const float *joints_px, const float *conf, const double *
  * weights, per-axis mean |error|, on the RAW tensors) and evaluate.py:91-125 (per-joint absolute and root-relative
  * PJPE with np.nansum semantics, per-axis distances with np.nanmean semantics, on the de-normalised tensors).
  * result (device, mpl_pose_metrics_size(J) floats): [0] loss, [1..3] loss per axis, [4..4+J) pjpe_abs, [4+J] mpjpe_abs,
- * [5+J..5+2J) pjpe_rel, [5+2J] mpjpe_rel, then dist (J x 3), dist_mean (3). */
+ * [5+J..5+2J) pjpe_rel, [5+2J] mpjpe_rel, then dist (J x 3), dist_mean (3).  1 <= joints <= 64. */
 int mpl_pose_metrics_size(int joints);
 int mpl_pose_metrics(const float *output, const float *target, const float *weight, int batch, int joints,
                      const float *scale3, const float *offset3, float *result, void *stream);
 /* The same with config.NOT_CONSIDER_SOME_KP_IN_EVAL (evaluate.py:101-104, :110-113): bit j of not_consider_mask set = joint j is
- * deleted from the two MEANS over joints (mpjpe_abs, mpjpe_rel); the per-joint errors are reported unchanged. */
+ * deleted from the two MEANS over joints (mpjpe_abs, mpjpe_rel); the per-joint errors are reported unchanged.  The mask has 32 bits:
+ * it can name joints 0..31 only, joints 32..63 of a larger skeleton always count. */
 int mpl_pose_metrics_ex(const float *output, const float *target, const float *weight, int batch, int joints,
                         const float *scale3, const float *offset3, uint32_t not_consider_mask, float *result, void *stream);
 

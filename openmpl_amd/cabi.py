@@ -14,7 +14,7 @@ from . import build as _build
 
 MPL_MAX_VIEWS = 32
 MPL_MAX_APPS = 64
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 # flag bits (mpl_hip.h MPL_F_*)
 F_MULTI_SPT = 1 << 0
@@ -30,6 +30,7 @@ F_NO_FPT = 1 << 9
 F_CONF_IN_FPT = 1 << 10
 F_KPTOK = 1 << 11
 F_NO_SMALL_STACK = 1 << 12
+F_GENERIC_SPT = 1 << 13
 # mpl_block_stack_form(): the kernel form a block stack of a given shape takes (MPL_FORM_* of mpl_hip.h) and the kernel behind it
 FORM_UNPACKED, FORM_SMALL, FORM_TEAMS, FORM_PAIRS, FORM_ROWS32, FORM_ROWS16, FORM_ROWS16_DIRECT, FORM_PER_GEMM = range(8)
 FORM_KERNELS = {FORM_UNPACKED: "ln_gemm_ng_kernel", FORM_SMALL: "sm_stack_kernel", FORM_TEAMS: "h2_stack_kernel<%d>", FORM_PAIRS: "h2_stack2_kernel<2>",
@@ -78,7 +79,7 @@ class Inputs(C.Structure):
                 ("poses", _fp * MPL_MAX_VIEWS), ("rays", _fp * MPL_MAX_VIEWS), ("centers", _fp * MPL_MAX_VIEWS)]
 
 
-EXPORTS = ("mpl_hip_abi_version", "mpl_hip_error_string", "mpl_fpt_width", "mpl_forward_workspace_bytes",
+EXPORTS = ("mpl_hip_abi_version", "mpl_hip_error_string", "mpl_config_supported", "mpl_fpt_width", "mpl_forward_workspace_bytes",
            "mpl_forward", "mpl_spt_tokens", "mpl_block_stack_workspace_bytes", "mpl_block_stack", "mpl_block_stack_ex",
            "mpl_ln_linear", "mpl_spt_pack_bytes", "mpl_spt_pack", "mpl_d32_pack", "mpl_pack_bf16_bytes", "mpl_pack_bf16", "mpl_pack_h2_bytes", "mpl_pack_h2", "mpl_pack_h2_scaled", "mpl_pack_h2_out_scale", "mpl_ln_linear_h2_workspace_bytes", "mpl_ln_linear_h2", "mpl_x3_debug_buffer", "mpl_x3_stack_mode", "mpl_block_stack_form", "mpl_block_stack_form_ex", "mpl_block_stack_last_form", "mpl_device_error", "mpl_device_error_clear", "mpl_x3_spin_limit", "mpl_token_attention", "mpl_fuse_head", "mpl_view_fuse", "mpl_view_norm",
            "mpl_layernorm", "mpl_linear", "mpl_pose_metrics_size", "mpl_pose_metrics", "mpl_pose_metrics_ex", "mpl_prepare_inputs", "mpl_profile_start",
@@ -128,6 +129,8 @@ def load():
                                % (lib.mpl_hip_abi_version(), ABI_VERSION))
         lib.mpl_hip_error_string.restype = C.c_char_p
         lib.mpl_hip_error_string.argtypes = [C.c_int]
+        lib.mpl_config_supported.restype = C.c_int
+        lib.mpl_config_supported.argtypes = [C.POINTER(Config)]
         lib.mpl_fpt_width.restype = C.c_int
         lib.mpl_fpt_width.argtypes = [C.POINTER(Config)]
         lib.mpl_forward_workspace_bytes.restype = C.c_size_t

@@ -307,7 +307,7 @@ int block_stack_impl(float* x, int n_seq, int n_tok, int D, int H, const mpl_blo
     int rc;
     // LayerNorm statistics are produced by whoever writes x: a stand-alone pass for the incoming x, then the
     // epilogues of proj (-> norm2) and fc2 (-> norm1 of the next application).
-    float* st_out = (D % 136 == 0) ? w.stats : nullptr;
+    float* st_out = (D % 136 == 0 && D % 32 == 0) ? w.stats : nullptr;      // (a width the tuned GEMMs take: launch_ln_gemm)
     bool have_stats = false;
     // qkv projection and attention run as one kernel when a 64-row tile holds whole sequences and a 136-column
     // slice whole heads (V in {1,2,4,8,16,32,64}; hd in {68,136}); otherwise as two kernels through `qkv`
@@ -389,6 +389,12 @@ int check_cfg(const mpl_config* cfg) {
     return MPL_OK;
 }
 
+// the joints x views token grid of a keypoint-token FPT: the attention kernels that take it (launch_token_attention)
+bool kptok_attention_ok(int n_tok, int hd) {
+    if (n_tok <= 32) return true;                                  // short attention: any head dim
+    return (hd == 4 || hd == 8) && (size_t)n_tok * hd * 8 <= 64 * 1024;
+}
+
 }  // namespace
 
 extern "C" {
@@ -441,6 +447,21 @@ const char* mpl_hip_error_string(int code) {
     }
 }
 
+int mpl_config_supported(const mpl_config* cfg) {
+    if (!cfg) return MPL_E_INVALID;
+    const unsigned f = cfg->flags;
+    const int J = cfg->num_joints, d = cfg->dim, H = cfg->heads, V = cfg->num_views;
+    if (J < 1 || J > 64 || d < 1 || d > 128 || H < 1 || d % H) return MPL_E_UNSUPPORTED;
+    if (V < 1 || V > MPL_MAX_VIEWS || cfg->depth < 0 || cfg->depth > 60) return MPL_E_UNSUPPORTED;
+    if ((f & MPL_F_CONF_ATTN_W) && !(f & MPL_F_NO_SPT) && cfg->depth > 31) return MPL_E_UNSUPPORTED;    // SPT schedule length
+    if ((long long)J * d * ((f & MPL_F_RAYS_TOKEN) ? 2 : 1) > 4096) return MPL_E_UNSUPPORTED;
+    if ((f & MPL_F_POS3D_TO_RAYS) && (!(f & MPL_F_RAYS_TOKEN) || (f & MPL_F_POS3D_SPATIAL))) return MPL_E_UNSUPPORTED;
+    if ((f & MPL_F_KPTOK) && !(f & MPL_F_NO_FPT) && cfg->depth > 0) {
+        if ((f & MPL_F_RAYS_TOKEN) || !kptok_attention_ok(J * V, d / H)) return MPL_E_UNSUPPORTED;
+    }
+    return MPL_OK;
+}
+
 int mpl_fpt_width(const mpl_config* cfg) {
     if (!cfg) return MPL_E_INVALID;
     return cfg->num_joints * cfg->dim * ((cfg->flags & MPL_F_RAYS_TOKEN) ? 2 : 1);
@@ -463,6 +484,7 @@ int mpl_spt_tokens(const mpl_config* cfg, const mpl_weights* w, const mpl_inputs
     clear_stale_hip_error();
     int rc = check_cfg(cfg);
     if (rc) return rc;
+    if ((rc = mpl_config_supported(cfg))) return rc;
     if (!w || !in || !xs) return MPL_E_INVALID;
     return launch_spt(cfg, w, in, xs, w->spt_packed != 0, (hipStream_t)stream);
 }
@@ -687,6 +709,7 @@ int mpl_forward(const mpl_config* cfg, const mpl_weights* w, const mpl_inputs* i
     clear_stale_hip_error();
     int rc = check_cfg(cfg);
     if (rc) return rc;
+    if ((rc = mpl_config_supported(cfg))) return rc;
     if ((rc = earlier_device_failure())) return rc;
     if (!w || !in || !out || in->batch <= 0) return MPL_E_INVALID;
     if ((long long)in->batch * cfg->num_views * cfg->num_joints > (1ll << 30)) return MPL_E_UNSUPPORTED;

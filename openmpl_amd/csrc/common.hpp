@@ -261,6 +261,8 @@ int launch_token_attention(const float* qkv, int n_seq, int n_tok, int dim, int 
 // use_packed: every SPT block carries the split operand of mpl_spt_pack in qkv_w3 (spt3_kernel: Linear layers on the bf16
 // matrix cores); else the fp32-MFMA kernel reads the nn.Linear weights in place
 int launch_spt(const mpl_config* cfg, const mpl_weights* w, const mpl_inputs* in, float* xs, int use_packed, hipStream_t s);
+// any J / d / H inside mpl_config_supported (spt_any.hip): fp32 FMA, the nn.Linear weights read in place
+int launch_spt_any(const mpl_config* cfg, const mpl_weights* w, const mpl_inputs* in, float* xs, hipStream_t s);
 size_t spt_pack_bytes();
 int launch_spt_pack(const mpl_block_weights* bw_host, unsigned short* dst, int fold_q, hipStream_t s);
 int launch_d32_qkv(const float* x, int M, const unsigned short* pack, float* qkv, hipStream_t s);

@@ -167,7 +167,8 @@ __device__ __forceinline__ void fh_linear(const FhParams& p, const float* hws, c
 // host side: the parameters of the default tail from the boundary structs; false = this shape has no fused / LDS form
 inline bool fh_params(const mpl_config* cfg, const mpl_weights* w, FhParams* p) {
     const int J = cfg->num_joints, d = cfg->dim, V = cfg->num_views, E = J * d;
-    if (E > kMaxE || E > 64 * FH_NF || V > MPL_MAX_VIEWS || 3 * J * E > FH_W_FLOATS || (E & 1)) return false;
+    // (the weight is staged in 16-byte pieces: 3J * E must be a multiple of 4, fh_stage_weight)
+    if (E > kMaxE || E > 64 * FH_NF || V > MPL_MAX_VIEWS || 3 * J * E > FH_W_FLOATS || (E & 1) || ((3 * J * E) & 3)) return false;
     int strip = 0;
     if (cfg->flags & MPL_F_POS3D_TO_RAYS) strip = 1;           // :430-434 (takes precedence, elif order)
     else if (cfg->flags & MPL_F_RAYS_TOKEN) strip = 2;         // :425-429

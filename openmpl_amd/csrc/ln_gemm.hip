@@ -74,10 +74,37 @@ __global__ __launch_bounds__(256) void row_stats32_kernel(const float* __restric
     }
 }
 
+// rows whose width or stride is not a multiple of 4 (FPT widths J*d of the shape-general models): scalar loads, same arithmetic
+__global__ __launch_bounds__(256) void row_stats_any_kernel(const float* __restrict__ x, int M, int K, int ldx, int sl,
+                                                             float* __restrict__ stats) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= M) return;
+    const int ns = K / sl;
+    for (int sidx = 0; sidx < ns; ++sidx) {
+        const float* xr = x + (size_t)row * ldx + (size_t)sidx * sl;
+        float s = 0.f;
+        for (int i = lane; i < sl; i += 64) s += xr[i];
+        const float mean = wave_sum(s) / (float)sl;
+        float ss = 0.f;
+        for (int i = lane; i < sl; i += 64) {
+            const float a = xr[i] - mean;
+            ss += a * a;
+        }
+        ss = wave_sum(ss);
+        if (lane == 0) {
+            stats[((size_t)row * ns + sidx) * 2] = mean;
+            stats[((size_t)row * ns + sidx) * 2 + 1] = ss;
+        }
+    }
+}
+
 int launch_row_stats(const float* x, int M, int K, int ldx, float* stats, hipStream_t s) {
-    if (M <= 0 || (K & 3)) return MPL_E_INVALID;
+    if (M <= 0 || K <= 0) return MPL_E_INVALID;
     ProfScope prof(MPL_K_ROW_STATS, s);
-    if (K == 32 && (ldx & 3) == 0)
+    if ((K & 3) || (ldx & 3))
+        hipLaunchKernelGGL(row_stats_any_kernel, dim3((M + 3) / 4), dim3(256), 0, s, x, M, K, ldx, ln_slice_len(K), stats);
+    else if (K == 32 && (ldx & 3) == 0)
         hipLaunchKernelGGL(row_stats32_kernel, dim3((int)(((size_t)M * 8 + 255) / 256)), dim3(256), 0, s, x, M, ldx, stats);
     else
         hipLaunchKernelGGL(row_stats_kernel, dim3((M + 3) / 4), dim3(256), 0, s, x, M, K, ldx, ln_slice_len(K), stats);
@@ -627,11 +654,11 @@ static int launch_ng_auto(const float* A, int lda, const float* stats, const flo
 }
 
 // LN1 + qkv projection + softmax attention in one launch: att[M, D] from x[M, D].  Requirements (else the caller
-// uses the separate kernels): 136 % hd == 0, 64 % n_tok == 0, D % 136 == 0.
+// uses the separate kernels): 136 % hd == 0, 64 % n_tok == 0, D % 136 == 0 and D % 32 == 0 (whole k-tiles).
 bool qkv_attention_fusable(int n_tok, int dim, int heads) {
     if (heads <= 0 || dim % heads) return false;
     const int hd = dim / heads;
-    return dim % BN == 0 && BN % hd == 0 && (hd & 3) == 0 && n_tok >= 1 && BM % n_tok == 0 && n_tok * n_tok * (BN / hd) * (BM / n_tok) <= ATT_SCORE_FLOATS;
+    return dim % BN == 0 && dim % BK == 0 && BN % hd == 0 && (hd & 3) == 0 && n_tok >= 1 && BM % n_tok == 0 && n_tok * n_tok * (BN / hd) * (BM / n_tok) <= ATT_SCORE_FLOATS;
 }
 
 int launch_ln_qkv_attention(const float* x, int M, int D, const float* stats, const float* ln_w, const float* ln_b,
@@ -643,14 +670,111 @@ int launch_ln_qkv_attention(const float* x, int M, int D, const float* stats, co
 }
 
 
+// ------------------------------------------------------------------------------------------
+// Any K, any leading dimension: the GEMMs of FPT widths the kernels above refuse (K % 32 != 0, e.g. J*d = 34 at d = 2 or 136 in the
+// micro model).  A 64 x 64 output tile per 256-thread workgroup, 32-deep k chunks of A (LayerNorm applied while staging) and W in
+// LDS, thread (tr, tc) owns rows tr + 16 q and columns tc + 16 u; products are a plain fmaf chain in k order.  No statistics
+// epilogue (the caller runs launch_row_stats instead).
+constexpr int AG_T = 64, AG_KC = 32, AG_S = AG_KC + 1;
+
+template <int EPI, bool LN>
+__global__ __launch_bounds__(256) void ln_gemm_any_kernel(const float* __restrict__ A, int lda, const float* __restrict__ stats,
+                                                          const float* __restrict__ ln_w, const float* __restrict__ ln_b, float eps,
+                                                          const float* __restrict__ W, const float* __restrict__ bias,
+                                                          const float* R, int ldr, float* C, int ldc, int M, int N, int K, int ns,
+                                                          int sl) {
+    __shared__ float As[AG_T * AG_S], Ws[AG_T * AG_S], mu_s[AG_T], rs_s[AG_T];
+    const int tid = threadIdx.x, tc = tid & 15, tr = tid >> 4;
+    const int row0 = blockIdx.y * AG_T, n0 = blockIdx.x * AG_T;
+    if (LN && tid < AG_T) {
+        float mu = 0.f, rs = 1.f;
+        if (row0 + tid < M) ln_combine(stats + (size_t)(row0 + tid) * ns * 2, ns, sl, K, eps, mu, rs);
+        mu_s[tid] = mu;
+        rs_s[tid] = rs;
+    }
+    float acc[4][4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int u = 0; u < 4; ++u) acc[q][u] = 0.f;
+    for (int k0 = 0; k0 < K; k0 += AG_KC) {
+        __syncthreads();
+        for (int i = tid; i < AG_T * AG_KC; i += 256) {
+            const int r = i / AG_KC, k = i - r * AG_KC, kk = k0 + k;
+            float a = 0.f, w = 0.f;
+            if (row0 + r < M && kk < K) {
+                a = A[(size_t)(row0 + r) * lda + kk];
+                if (LN) a = (a - mu_s[r]) * rs_s[r] * ln_w[kk] + ln_b[kk];
+            }
+            if (n0 + r < N && kk < K) w = W[(size_t)(n0 + r) * K + kk];
+            As[r * AG_S + k] = a;
+            Ws[r * AG_S + k] = w;
+        }
+        __syncthreads();
+#pragma unroll 4
+        for (int k = 0; k < AG_KC; ++k) {
+            float a[4], w[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) a[q] = As[(tr + 16 * q) * AG_S + k];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) w[u] = Ws[(tc + 16 * u) * AG_S + k];
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+#pragma unroll
+                for (int u = 0; u < 4; ++u) acc[q][u] = fmaf(a[q], w[u], acc[q][u]);
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int r = row0 + tr + 16 * q;
+        if (r >= M) continue;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int n = n0 + tc + 16 * u;
+            if (n >= N) continue;
+            float v = acc[q][u] + bias[n];
+            if (EPI == MPL_EPI_BIAS_GELU) v = gelu_erf(v);
+            if (EPI == MPL_EPI_BIAS_RESIDUAL) v += R[(size_t)r * ldr + n];
+            C[(size_t)r * ldc + n] = v;
+        }
+    }
+}
+
+template <int EPI>
+static int launch_ln_gemm_any(const float* A, int lda, const float* stats, const float* ln_w, const float* ln_b, float eps,
+                              const float* W, const float* bias, const float* R, int ldr, float* C, int ldc, int M, int N, int K,
+                              hipStream_t s) {
+    const dim3 grid((unsigned)((N + AG_T - 1) / AG_T), (unsigned)((M + AG_T - 1) / AG_T));
+    if (grid.y > 65535u) return MPL_E_UNSUPPORTED;
+    ProfScope prof(MPL_K_GEMM, s);
+    if (ln_w)
+        hipLaunchKernelGGL((ln_gemm_any_kernel<EPI, true>), grid, dim3(256), 0, s, A, lda, stats, ln_w, ln_b, eps, W, bias, R, ldr, C,
+                           ldc, M, N, K, ln_stat_slices(K), ln_slice_len(K));
+    else
+        hipLaunchKernelGGL((ln_gemm_any_kernel<EPI, false>), grid, dim3(256), 0, s, A, lda, stats, ln_w, ln_b, eps, W, bias, R, ldr,
+                           C, ldc, M, N, K, 1, K);
+    return hip_check_launch();
+}
+
 int launch_ln_gemm(const float* A, int lda, const float* stats, const float* ln_w, const float* ln_b, float eps,
                    const float* W, const float* bias, const float* R, int ldr, float* C, int ldc, int M, int N, int K,
                    int epi, float* stats_out, hipStream_t s) {
-    if (M <= 0 || N <= 0 || K <= 0 || (K % BK) != 0 || (lda & 3)) return MPL_E_INVALID;
+    if (M <= 0 || N <= 0 || K <= 0) return MPL_E_INVALID;
     const bool ln = ln_w != nullptr;
     if (ln && (!stats || !ln_b)) return MPL_E_INVALID;
     if (epi == MPL_EPI_BIAS_RESIDUAL && !R) return MPL_E_INVALID;
     if (stats_out && (epi != MPL_EPI_BIAS_RESIDUAL || N % BN != 0)) return MPL_E_INVALID;
+    if ((K % BK) != 0 || (lda & 3)) {        // shapes the tuned kernels below do not take
+        if (stats_out) return MPL_E_INVALID;
+        switch (epi) {
+            case MPL_EPI_BIAS: return launch_ln_gemm_any<MPL_EPI_BIAS>(A, lda, stats, ln_w, ln_b, eps, W, bias, R, ldr, C, ldc, M, N, K, s);
+            case MPL_EPI_BIAS_GELU:
+                return launch_ln_gemm_any<MPL_EPI_BIAS_GELU>(A, lda, stats, ln_w, ln_b, eps, W, bias, R, ldr, C, ldc, M, N, K, s);
+            case MPL_EPI_BIAS_RESIDUAL:
+                return launch_ln_gemm_any<MPL_EPI_BIAS_RESIDUAL>(A, lda, stats, ln_w, ln_b, eps, W, bias, R, ldr, C, ldc, M, N, K, s);
+            default: return MPL_E_INVALID;
+        }
+    }
 #define MPL_ARGS A, lda, stats, ln_w, ln_b, W, bias, R, ldr, C, ldc, M, N, K, eps, stats_out, s
 #define MPL_GEMM_CASE(E)                                                                              \
     case E:                                                                                           \

@@ -11,10 +11,11 @@
 
 namespace mpl {
 
-constexpr int MJ = 17;  // joints handled per thread row (J <= 17)
-constexpr int MS = 15;  // batch slices: 17 * 15 = 255 threads
+// Two geometries of the same kernel: MJ = 17 joints x MS = 15 batch slices (255 threads, every J <= 17) and 64 x 4 for
+// 18 <= J <= 64.
 constexpr int MACC = 12;
 
+template <int MJ, int MS>
 __global__ __launch_bounds__(256) void pose_metrics_kernel(const float* __restrict__ out, const float* __restrict__ tgt,
                                                             const float* __restrict__ wgt, int B, int J, float sx, float sy,
                                                             float sz, float ox, float oy, float oz, unsigned skip_mask,
@@ -83,7 +84,7 @@ __global__ __launch_bounds__(256) void pose_metrics_kernel(const float* __restri
         int kept = 0;          // evaluate.py:101-104, :110-113: joints in not_consider_kp are deleted from the MEAN only
         for (int q = 0; q < J; ++q) {
             loss += acc[0][q][0];
-            if (!((skip_mask >> q) & 1u)) {
+            if (q >= 32 || !((skip_mask >> q) & 1u)) {      // the mask covers joints 0..31
                 ma += acc[0][q][4] / B;
                 mr += acc[0][q][5] / B;
                 ++kept;
@@ -105,13 +106,18 @@ __global__ __launch_bounds__(256) void pose_metrics_kernel(const float* __restri
 
 int launch_pose_metrics(const float* out, const float* tgt, const float* wgt, int B, int J, const float* scale3,
                         const float* offset3, unsigned skip_mask, float* res, hipStream_t s) {
-    if (!out || !tgt || !res || B <= 0 || J <= 0 || J > MJ) return MPL_E_INVALID;
+    if (!out || !tgt || !res || B <= 0 || J <= 0 || J > 64) return MPL_E_INVALID;
     const float sx = scale3 ? scale3[0] : 1.f, sy = scale3 ? scale3[1] : 1.f, sz = scale3 ? scale3[2] : 1.f;
     const float ox = offset3 ? offset3[0] : 0.f, oy = offset3 ? offset3[1] : 0.f, oz = offset3 ? offset3[2] : 0.f;
     int dev = 0;
     const unsigned* dev_err = hipGetDevice(&dev) == hipSuccess ? device_error_word(dev) : nullptr;
     ProfScope prof(MPL_K_FUSE_HEAD, s);
-    hipLaunchKernelGGL(pose_metrics_kernel, dim3(1), dim3(256), 0, s, out, tgt, wgt, B, J, sx, sy, sz, ox, oy, oz, skip_mask, dev_err, res);
+    if (J <= 17)
+        hipLaunchKernelGGL((pose_metrics_kernel<17, 15>), dim3(1), dim3(256), 0, s, out, tgt, wgt, B, J, sx, sy, sz, ox, oy, oz, skip_mask,
+                           dev_err, res);
+    else
+        hipLaunchKernelGGL((pose_metrics_kernel<64, 4>), dim3(1), dim3(256), 0, s, out, tgt, wgt, B, J, sx, sy, sz, ox, oy, oz, skip_mask,
+                           dev_err, res);
     return hip_check_launch();
 }
 

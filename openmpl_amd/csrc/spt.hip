@@ -1348,7 +1348,9 @@ int launch_d32_mlp(float* x, const float* att, int M, const unsigned short* pack
 }
 
 int launch_spt(const mpl_config* cfg, const mpl_weights* w, const mpl_inputs* in, float* xs, int use_packed, hipStream_t s) {
-    if (cfg->num_joints != SJ || cfg->dim != SD || cfg->heads != SH) return MPL_E_UNSUPPORTED;
+    // every other shape, and 17 / 32 / 8 on request, runs on the shape-general kernel (spt_any.hip)
+    if (cfg->num_joints != SJ || cfg->dim != SD || cfg->heads != SH || (cfg->flags & MPL_F_GENERIC_SPT))
+        return launch_spt_any(cfg, w, in, xs, s);
     if (cfg->num_views < 1 || cfg->num_views > MPL_MAX_VIEWS || in->batch <= 0) return MPL_E_INVALID;
     if (cfg->in_chans != 2 && cfg->in_chans != 3) return MPL_E_INVALID;
     const unsigned f = cfg->flags;

@@ -437,10 +437,72 @@ __global__ __launch_bounds__(256) void token_attention_long_p4_kernel(const floa
     }
 }
 
+// The same for head dims that are not a multiple of 4 (FPT widths J*d of the shape-general models, e.g. hd = 17 at d = 2, H = 2):
+// scalar loads, one thread per (query row, head), up to 32 tokens.
+template <int VT>
+__global__ __launch_bounds__(256) void token_attention_any_kernel(const float* __restrict__ qkv, float* __restrict__ out, int n_seq,
+                                                                   int n_tok, int D, int H, float scale) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= n_seq * n_tok * H) return;
+    const int h = idx % H;
+    const int i = (idx / H) % n_tok;
+    const int sq = idx / (H * n_tok);
+    const int hd = D / H;
+    const size_t ld = (size_t)3 * D;
+    const float* base = qkv + (size_t)sq * n_tok * ld + (size_t)h * hd;
+    const float* q = base + (size_t)i * ld;
+    float sc[VT];
+#pragma unroll
+    for (int j = 0; j < VT; ++j) {
+        sc[j] = -INFINITY;
+        if (j < n_tok) {
+            const float* k = base + (size_t)j * ld + D;
+            float a = 0.f;
+            for (int e = 0; e < hd; ++e) a = fmaf(q[e], k[e], a);
+            sc[j] = a * scale;
+        }
+    }
+    float mx = sc[0];
+#pragma unroll
+    for (int j = 1; j < VT; ++j) mx = fmaxf(mx, sc[j]);
+    float l = 0.f;
+#pragma unroll
+    for (int j = 0; j < VT; ++j) {
+        sc[j] = (j < n_tok) ? __expf(sc[j] - mx) : 0.f;
+        l += sc[j];
+    }
+    const float inv = 1.0f / l;
+#pragma unroll
+    for (int j = 0; j < VT; ++j) sc[j] *= inv;
+    float* o = out + ((size_t)sq * n_tok + i) * D + (size_t)h * hd;
+    const float* v0 = base + 2 * D;
+    for (int e = 0; e < hd; ++e) {
+        float acc = 0.f;
+#pragma unroll
+        for (int j = 0; j < VT; ++j)
+            if (j < n_tok) acc = fmaf(sc[j], v0[(size_t)j * ld + e], acc);
+        o[e] = acc;
+    }
+}
+
 int launch_token_attention(const float* qkv, int n_seq, int n_tok, int dim, int heads, float* out, hipStream_t s) {
     if (n_seq <= 0 || n_tok <= 0 || heads <= 0 || dim % heads) return MPL_E_INVALID;
     const int hd = dim / heads;
-    if (hd & 3) return MPL_E_UNSUPPORTED;
+    if (hd & 3) {
+        if (n_tok > 32) return MPL_E_UNSUPPORTED;
+        const float scale = 1.0f / sqrtf((float)hd);
+        const long long total = (long long)n_seq * n_tok * heads;
+        if (total > 0x7fffffffll) return MPL_E_UNSUPPORTED;
+        ProfScope prof(MPL_K_ATTENTION, s);
+        const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+#define MPL_ATT(VT) hipLaunchKernelGGL((token_attention_any_kernel<VT>), grid, block, 0, s, qkv, out, n_seq, n_tok, dim, heads, scale)
+        if (n_tok <= 4) MPL_ATT(4);
+        else if (n_tok <= 8) MPL_ATT(8);
+        else if (n_tok <= 16) MPL_ATT(16);
+        else MPL_ATT(32);
+#undef MPL_ATT
+        return hip_check_launch();
+    }
     if (n_tok > 32) {
         if ((hd != 4 && hd != 8) || (size_t)n_tok * hd * 8 > 64 * 1024) return MPL_E_UNSUPPORTED;
         const float sc = 1.0f / sqrtf((float)hd);

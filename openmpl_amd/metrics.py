@@ -39,6 +39,8 @@ def pose_metrics(output: torch.Tensor, target: torch.Tensor, weight: Optional[to
     for k in (not_consider_kp if not_consider_kp is not None else ()):
         if not -J <= int(k) < J:
             raise IndexError("index %d is out of bounds for axis 0 with size %d" % (int(k), J))      # what np.delete raises
+        if int(k) % J >= 32:
+            raise NotImplementedError("not_consider_kp can name joints 0..31 only (a 32-bit mask in mpl_pose_metrics_ex)")
         mask |= 1 << (int(k) % J)
     with torch.cuda.device(output.device):
         rc = lib.mpl_pose_metrics_ex(output.data_ptr(), target.data_ptr(), None if weight is None else weight.data_ptr(), B, J,

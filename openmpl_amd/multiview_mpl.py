@@ -133,7 +133,7 @@ def _module_of(handle: int) -> "MultiView_MPL":
 
 @torch.library.custom_op("openmpl_amd::forward", mutates_args=(), device_types="cuda")
 def _forward_op(handle: int, poses: List[torch.Tensor], rays: List[torch.Tensor], centers: List[torch.Tensor]) -> List[torch.Tensor]:
-    """[poses (B,17,3)] of MultiView_MPL.forward (reference :450-525); with head_kadkhod [x3, x1, x2].  rays / centers: V tensors
+    """[poses (B,J,3)] of MultiView_MPL.forward (reference :450-525); with head_kadkhod [x3, x1, x2].  rays / centers: V tensors
     or an empty list (= None)."""
     m = _module_of(handle)
     out = m._forward_impl(list(poses), list(rays) or None, list(centers) or None)
@@ -316,20 +316,43 @@ class MultiView_MPL(nn.Module):
 
     # ------------------------------------------------------------------ support matrix
     def _find_unsupported(self) -> Optional[str]:
-        """Flag combinations the HIP path does not implement yet (they raise, they never fall back)."""
-        if self.num_joints != 17 or self.embed_dim_ratio != 32 or self.num_heads != 8:
-            return "HIP kernels are specialised for NUM_JOINTS=17, DIM=32, HEADS=8 (every shipped yaml)"
-        if self.num_views > cabi.MPL_MAX_VIEWS:
-            return "num_views > %d" % cabi.MPL_MAX_VIEWS
-        if self.FPT_blocks_view_keypoint_tokens and self.input_rays_as_token:
-            return "FPT_blocks_view_keypoint_tokens with input_rays_as_token (the reference itself fails: LN(32) on 64)"
-        if self.FPT_blocks_view_keypoint_tokens and self.num_joints * self.num_views * (self.embed_dim_ratio // self.num_heads) * 8 > 64 * 1024:
-            return "joints x views grid too long for the LDS-resident K/V of one head"
-        if self.add_3D_pos_encoding_to_rays and not self.input_rays_as_token:
-            return "add_3D_pos_encoding_to_rays without input_rays_as_token (the reference itself fails, :483)"
-        if self.add_3D_pos_encoding_to_rays and self.add_3D_pos_encoding_in_Spatial:
-            return "add_3D_pos_encoding_to_rays together with add_3D_pos_encoding_in_Spatial"
-        return None
+        """Configurations the HIP path does not implement (they raise, they never fall back).  The library decides
+        (mpl_config_supported, include/mpl_hip.h); this names the limit that was crossed."""
+        J, d, H, V = self.num_joints, self.embed_dim_ratio, self.num_heads, self.num_views
+        width = J * d * (2 if self.input_rays_as_token else 1)
+        kp_fpt = self.FPT_blocks_view_keypoint_tokens and not self.no_transformer_fpt and self.depth > 0
+        hd = d // H if H > 0 else 0
+        reason = None
+        if not 1 <= J <= 64:
+            reason = "NUM_JOINTS = %d outside 1..64" % J
+        elif not 1 <= d <= 128:
+            reason = "DIM = %d outside 1..128" % d
+        elif H < 1 or d % H:
+            reason = "DIM = %d is not a multiple of TRANSFORMER_HEADS = %d (the reference fails in the qkv reshape)" % (d, H)
+        elif width > 4096:
+            reason = "FPT width NUM_JOINTS x DIM%s = %d exceeds 4096" % (" x 2 (input_rays_as_token)" if self.input_rays_as_token else "",
+                                                                        width)
+        elif not 1 <= V <= cabi.MPL_MAX_VIEWS:
+            reason = "num_views = %d outside 1..%d" % (V, cabi.MPL_MAX_VIEWS)
+        elif not 0 <= self.depth <= 60:
+            reason = "depth = %d outside 0..60" % self.depth
+        elif self.confidence_as_attention_uncertainty_weight and not self.no_transformer_spt and self.depth > 31:
+            reason = "depth > 31 with confidence_as_attention_uncertainty_weight (SPT schedule longer than %d blocks)" % cabi.MPL_MAX_APPS
+        elif self.FPT_blocks_view_keypoint_tokens and self.input_rays_as_token:
+            reason = "FPT_blocks_view_keypoint_tokens with input_rays_as_token (the reference itself fails: LN(d) on 2d)"
+        elif kp_fpt and J * V > 32 and hd not in (4, 8):
+            reason = ("joints x views grid of %d tokens (> 32) needs head dim 4 or 8 for the long token attention (head dim %d)"
+                      % (J * V, hd))
+        elif kp_fpt and J * V > 32 and J * V * hd * 8 > 64 * 1024:
+            reason = "joints x views grid too long for the LDS-resident K/V of one head"
+        elif self.add_3D_pos_encoding_to_rays and not self.input_rays_as_token:
+            reason = "add_3D_pos_encoding_to_rays without input_rays_as_token (the reference itself fails, :483)"
+        elif self.add_3D_pos_encoding_to_rays and self.add_3D_pos_encoding_in_Spatial:
+            reason = "add_3D_pos_encoding_to_rays together with add_3D_pos_encoding_in_Spatial"
+        rc = cabi.load().mpl_config_supported(C.byref(self._config()))
+        if rc == 0:
+            return reason
+        return reason or "mpl_config_supported refuses this configuration (code %d)" % rc
 
     def set_matmul_precision(self, precision: str):
         """Arithmetic of the FPT block GEMMs (everything else is fp32 always):
@@ -358,7 +381,11 @@ class MultiView_MPL(nn.Module):
         if c is not None and c[0] == _STRUCT_GEN[0] and _HOOKS_OK:
             return c[1]
         ok = False
-        if not (self.no_transformer_fpt or len(self.blocks) == 0 or self.FPT_blocks_view_keypoint_tokens or self.num_views > 32):
+        D = self.blocks[0].attn.qkv.weight.shape[1] if len(self.blocks) else 0
+        hd = D // self.num_heads if D % self.num_heads == 0 else 0
+        # the packed stacks fuse qkv and attention: a head must tile the 136-column slice (hd 68 at every DIM-32 model)
+        fusable = hd > 0 and hd % 4 == 0 and 136 % hd == 0
+        if fusable and not (self.no_transformer_fpt or len(self.blocks) == 0 or self.FPT_blocks_view_keypoint_tokens or self.num_views > 32):
             lib = cabi.load()
             b = self.blocks[0]
             ok = all(lib.mpl_pack_bf16_bytes(int(t.shape[0]), int(t.shape[1])) > 0 and
@@ -507,10 +534,14 @@ class MultiView_MPL(nn.Module):
         h2 = self.matmul_precision == "fp32" and x3ok
         # the SPT Linear layers also run from split operands (fp32 arithmetic on the fp16 matrix cores) unless the native
         # fp32 matrix instructions were asked for
-        spt3 = self.matmul_precision != "fp32_mfma" and not self.no_transformer_spt
-        # keypoint-token FPT blocks (width 32 = the SPT block's shapes) run from the same kind of split operand (mpl_d32_pack)
-        d32 = self.matmul_precision == "fp32" and self.FPT_blocks_view_keypoint_tokens \
-            and not self.no_transformer_fpt and len(self.blocks) > 0 and tuple(self.blocks[0].attn.qkv.weight.shape) == (96, 32)
+        # (the tuned SPT kernels exist for NUM_JOINTS 17, DIM 32, HEADS 8 only; every other shape runs spt_any.hip on the tensors)
+        tuned = (self.num_joints, self.embed_dim_ratio, self.num_heads) == (17, 32, 8)
+        spt3 = self.matmul_precision != "fp32_mfma" and not self.no_transformer_spt and tuned
+        # keypoint-token FPT blocks (width 32, head dim 4 = the SPT block's shapes) run from the same kind of split operand
+        # (mpl_d32_pack)
+        d32 = self.matmul_precision == "fp32" and self.FPT_blocks_view_keypoint_tokens and self.embed_dim_ratio == 32 \
+            and self.num_heads == 8 and not self.no_transformer_fpt and len(self.blocks) > 0 \
+            and tuple(self.blocks[0].attn.qkv.weight.shape) == (96, 32)
         dkey = self._derived_key(h2, bf16, spt3, d32)
         key = tuple([t.data_ptr() for t in plist]) + dkey
         ent = self._hip_cache.get(device.index)
