@@ -262,6 +262,8 @@ int block_stack_impl(float* x, int n_seq, int n_tok, int D, int H, const mpl_blo
     // row counts are 32-bit in the kernels (byte offsets are 64-bit): refuse what would overflow instead of wrapping
     if ((long long)n_seq * n_tok > (1ll << 30)) return MPL_E_UNSUPPORTED;
     if (n_apps == 0) return MPL_OK;
+    // the narrowest GEMM of a block (K = D) decides whether the any-K kernel runs it, and it must take the rows
+    if (!ln_gemm_rows_ok((long long)n_seq * n_tok, D, D)) return MPL_E_UNSUPPORTED;
     if (!blocks || !schedule) return MPL_E_INVALID;
     const int np0 = stack_packed_parts(blocks, schedule, n_apps, n_tok, D, H);
     // up to 80 token rows (a single frame, a few frames): the whole chip on every GEMM instead of one team of D / 136
@@ -507,6 +509,7 @@ int mpl_ln_linear(const float* x, int M, int K, const float* ln_w, const float* 
                   void* stream) {
     clear_stale_hip_error();
     if (!x || !W || !bias || !y) return MPL_E_INVALID;
+    if (M > 0 && K > 0 && !ln_gemm_rows_ok(M, K, K)) return MPL_E_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
     if (ln_w) {
         if (!stats) return MPL_E_INVALID;
@@ -713,6 +716,11 @@ int mpl_forward(const mpl_config* cfg, const mpl_weights* w, const mpl_inputs* i
     if ((rc = earlier_device_failure())) return rc;
     if (!w || !in || !out || in->batch <= 0) return MPL_E_INVALID;
     if ((long long)in->batch * cfg->num_views * cfg->num_joints > (1ll << 30)) return MPL_E_UNSUPPORTED;
+    if (!(cfg->flags & MPL_F_NO_FPT) && cfg->depth > 0) {      // the block stack's GEMMs must take its rows (block_stack_impl)
+        const bool kp = (cfg->flags & MPL_F_KPTOK) != 0;
+        const int Ds = kp ? cfg->dim : mpl_fpt_width(cfg);
+        if (!ln_gemm_rows_ok((long long)in->batch * cfg->num_views * (kp ? cfg->num_joints : 1), Ds, Ds)) return MPL_E_UNSUPPORTED;
+    }
     const size_t need = mpl_forward_workspace_bytes(cfg, in->batch);
     if (!workspace || workspace_bytes < need) return MPL_E_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;

@@ -174,6 +174,9 @@ int launch_ln_gemm(const float* A, int lda, const float* stats, const float* ln_
                    const float* W, const float* bias, const float* R, int ldr, float* C, int ldc, int M, int N, int K,
                    int epi, float* stats_out, hipStream_t s);
 bool qkv_attention_fusable(int n_tok, int dim, int heads);
+// false: launch_ln_gemm refuses M rows of width K (the any-K kernel has one grid row per 64-row tile, at most 65535); callers that
+// launch anything before their GEMMs ask first, so that such a batch is refused before the first launch
+bool ln_gemm_rows_ok(long long M, int K, int lda);
 int launch_ln_qkv_attention(const float* x, int M, int D, const float* stats, const float* ln_w, const float* ln_b,
                             float eps, const float* W, const float* bias, int n_tok, int heads, float* att,
                             hipStream_t s);

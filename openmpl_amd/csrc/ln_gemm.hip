@@ -740,12 +740,14 @@ __global__ __launch_bounds__(256) void ln_gemm_any_kernel(const float* __restric
     }
 }
 
+bool ln_gemm_rows_ok(long long M, int K, int lda) { return ((K % BK) == 0 && (lda & 3) == 0) || (M + AG_T - 1) / AG_T <= 65535; }
+
 template <int EPI>
 static int launch_ln_gemm_any(const float* A, int lda, const float* stats, const float* ln_w, const float* ln_b, float eps,
                               const float* W, const float* bias, const float* R, int ldr, float* C, int ldc, int M, int N, int K,
                               hipStream_t s) {
+    if (!ln_gemm_rows_ok(M, K, lda)) return MPL_E_UNSUPPORTED;
     const dim3 grid((unsigned)((N + AG_T - 1) / AG_T), (unsigned)((M + AG_T - 1) / AG_T));
-    if (grid.y > 65535u) return MPL_E_UNSUPPORTED;
     ProfScope prof(MPL_K_GEMM, s);
     if (ln_w)
         hipLaunchKernelGGL((ln_gemm_any_kernel<EPI, true>), grid, dim3(256), 0, s, A, lda, stats, ln_w, ln_b, eps, W, bias, R, ldr, C,
