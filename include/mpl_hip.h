@@ -86,10 +86,14 @@ typedef struct mpl_block_weights {
     const float *fc1_w, *fc1_b;
     const float *fc2_w, *fc2_b;
     /* Optional packed bf16 operands (mpl_pack_bf16) of the four Linear layers: qkv built with norm1 folded, fc1 with norm2
-     * folded, proj / fc2 plain.  When all four are non-NULL in every block of a stack whose shape the engine supports (D a
-     * multiple of 544, n_tok <= 32), the stack's GEMMs run on the bf16 matrix cores with bf16 operands and fp32
+     * folded, proj / fc2 plain.  When all four are non-NULL in every block of a stack whose shape the engine supports (D 544
+     * or 1088, n_tok <= 32), the stack's GEMMs run on the bf16 matrix cores with bf16 operands and fp32
      * accumulation (activations handed from GEMM to GEMM as bf16; LayerNorm statistics, softmax, GELU, the residual
-     * stream and the output stay fp32) -- BASELINE.json configs[2] "bf16".  The fp32 tensors remain the source of truth. */
+     * stream and the output stay fp32) -- BASELINE.json configs[2] "bf16".  The fp32 tensors remain the source of truth.
+     * For every other stack shape of up to 32 tokens per sequence (any width up to 4096, any head count that divides it) the
+     * same four fields carry the shape-general operands of mpl_pack_bf16_any instead, and the stack runs one plain launch per
+     * GEMM (csrc/b1_any.hip, same rounding points).  mpl_bf16_operand_layout(dim, heads, n_tok) says which of the two layouts a
+     * stack expects: the library launches by it, whoever packs must pack by it. */
     const uint16_t *qkv_w16, *proj_w16, *fc1_w16, *fc2_w16;
     /* qkv_w3: the row-local split operand of a d = 32 block (mpl_spt_pack for the SPT blocks of an mpl_spt_set, mpl_d32_pack for
      * the keypoint-token FPT blocks); proj_w3 / fc1_w3 / fc2_w3 are unused and must be NULL (they carried the three-part bf16
@@ -222,6 +226,33 @@ size_t mpl_pack_bf16_bytes(int N, int K);
 int mpl_pack_bf16(const float *W, const float *bias, const float *ln_w, const float *ln_b, int N, int K, uint16_t *dst,
                   void *stream);
 
+/* Which packed bf16 operands the *_w16 fields of a block stack of this shape carry -- ONE rule, by which mpl_block_stack launches and
+ * a binding packs: MPL_BF16_TUNED = mpl_pack_bf16 (the team kernels take the shape: dim 544 or 1088, a head that tiles a
+ * 136-column slice, n_tok <= 32); MPL_BF16_ANY = mpl_pack_bf16_any (every other dim <= 4096 with dim % heads == 0 and n_tok <= 32);
+ * MPL_BF16_NONE = the shape has no bf16 engine (more than 32 tokens per sequence: the joints x views token grid).  No device needed. */
+enum { MPL_BF16_NONE = 0, MPL_BF16_TUNED = 1, MPL_BF16_ANY = 2 };
+int mpl_bf16_operand_layout(int dim, int heads, int n_tok);
+
+/* Packed bf16 operand of an nn.Linear layer (W[N][K], bias[N]) for the shape-general bf16 engine (csrc/b1_any.hip), any
+ * 1 <= N <= 16384, 1 <= K <= 8192: bf16(gamma o W) (round to nearest even of the fp32 product; gamma = 1 without a LayerNorm) as
+ * [ceil(N/64)][ceil(K/32)][4 column tiles][64 lanes][8 bf16] -- lane l, element j of column tile t of block (nb, kt) is
+ * W[64 nb + 16 t + (l & 15)][32 kt + 8 (l >> 4) + j], ZERO where that is beyond N or K -- followed by the fp32 vectors
+ * c[N] = bias + W . beta and s[N] = sum_k of the ROUNDED gamma_k W_nk (c = bias, s = 0 without a LayerNorm), padded to 16 bytes.
+ * ln_w and ln_b come together or not at all.  mpl_pack_bf16_any_bytes() = size of `dst`, 0 outside the limits above.  `dst` must be
+ * 16-byte aligned (it is written and read as 16-byte fragments; MPL_E_INVALID otherwise). */
+size_t mpl_pack_bf16_any_bytes(int N, int K);
+int mpl_pack_bf16_any(const float *W, const float *bias, const float *ln_w, const float *ln_b, int N, int K, uint16_t *dst,
+                      void *stream);
+/* ONE GEMM of that engine, the unit-test entry (the forward reaches the kernel through mpl_block_stack):
+ *   has_ln != 0: y = epi(rstd (bf16(x) . W16^T - mean s) + c) on the raw fp32 rows x[M][K]; stats = 2 * M * max(1, K / 136) floats of
+ *     scratch; epilogue MPL_EPI_BIAS -> y fp32 [M][N], MPL_EPI_BIAS_GELU -> y bf16 (uint16_t) [M][N] = bf16(gelu_erf(.));
+ *   has_ln == 0: y = residual + bf16(x) . W16^T + c, epilogue MPL_EPI_BIAS_RESIDUAL only (residual may alias y); x is rounded to
+ *     bf16 rows in `workspace` (mpl_ln_linear_bf16_any_workspace_bytes(M, K), 16-byte aligned) first.
+ * Other combinations are MPL_E_UNSUPPORTED: a Block has no other. */
+size_t mpl_ln_linear_bf16_any_workspace_bytes(int M, int K);
+int mpl_ln_linear_bf16_any(const float *x, int M, int K, int has_ln, float eps, const uint16_t *W16, int N, int epilogue,
+                           const float *residual, void *y, float *stats, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Diagnostics (tools/chain_phase.py): when non-NULL, every packed-operand GEMM launch writes five shader-clock stamps per
  * wave (entry, k-loop start, k-loop end, stores issued, stores drained) at device_buffer[(block * 8 + wave) * 8 ..];
  * the buffer must hold 64 bytes per wave of the largest launch.  NULL (the default) switches it off.  The stamps are
@@ -242,7 +273,8 @@ int mpl_x3_stack_mode(int one_launch_per_gemm);
 
 /* Which kernel form mpl_block_stack(_ex) takes for a stack of this shape on the current device, by the library's own rule
  * (csrc/h2_phase.hpp h2_stack_form, csrc/api.hip block_stack_impl): for benchmarks that name the kernel they time and tests that
- * pin the rule.  operand_parts: 2 = the blocks carry mpl_pack_h2 operands, 1 = mpl_pack_bf16, 0 = neither; `flags` as
+ * pin the rule.  operand_parts: 2 = the blocks carry mpl_pack_h2 operands, 1 = bf16 operands in their *_w16 fields (in the layout
+ * mpl_bf16_operand_layout names for the shape), 0 = neither; `flags` as
  * mpl_config.flags (MPL_F_NO_SMALL_STACK).  The small-batch engine additionally needs the nn.Linear tensors of the blocks
  * (the query assumes they are there).  Negative = MPL_E_*.  Every team form yields bitwise the same poses. */
 enum {
@@ -253,7 +285,8 @@ enum {
     MPL_FORM_ROWS32 = 4,          /* h2_stackn_kernel<2>: 32-row teams */
     MPL_FORM_ROWS16 = 5,          /* h2_stackn_kernel<2>: 16-row teams, ring form (A/B, or A operand too large for LDS) */
     MPL_FORM_ROWS16_DIRECT = 6,   /* h2_stackd_kernel<2>: 16-row teams, direct-W form */
-    MPL_FORM_PER_GEMM = 7         /* h2_gemm_kernel: one launch per GEMM (mpl_x3_stack_mode bit 0) */
+    MPL_FORM_PER_GEMM = 7,        /* h2_gemm_kernel: one launch per GEMM (mpl_x3_stack_mode bit 0) */
+    MPL_FORM_BF16_ANY = 8         /* b1a_gemm_kernel: bf16 operands of mpl_pack_bf16_any, one launch per GEMM (any width) */
 };
 int mpl_block_stack_form(int n_seq, int n_tok, int D, int heads, int n_apps, int operand_parts, unsigned flags);
 /* The same question with everything the launch rule looks at: n_blocks = distinct blocks the schedule indexes (mpl_block_stack_form
@@ -377,7 +410,7 @@ int mpl_x3_spin_limit(int log2_polls);
 #define MPL_K_GEMM 2
 #define MPL_K_ATTENTION 3
 #define MPL_K_FUSE_HEAD 4
-#define MPL_K_PACK 5 /* derived-operand builders: mpl_pack_h2*, mpl_spt_pack, mpl_d32_pack, mpl_pack_bf16 */
+#define MPL_K_PACK 5 /* derived-operand builders: mpl_pack_h2*, mpl_spt_pack, mpl_d32_pack, mpl_pack_bf16(_any) */
 #define MPL_K_COUNT 6
 int mpl_profile_start(void);
 int mpl_profile_stop(float *kind_ms, int *kind_launches, int n_kinds);

@@ -32,10 +32,12 @@ F_KPTOK = 1 << 11
 F_NO_SMALL_STACK = 1 << 12
 F_GENERIC_SPT = 1 << 13
 # mpl_block_stack_form(): the kernel form a block stack of a given shape takes (MPL_FORM_* of mpl_hip.h) and the kernel behind it
-FORM_UNPACKED, FORM_SMALL, FORM_TEAMS, FORM_PAIRS, FORM_ROWS32, FORM_ROWS16, FORM_ROWS16_DIRECT, FORM_PER_GEMM = range(8)
+FORM_UNPACKED, FORM_SMALL, FORM_TEAMS, FORM_PAIRS, FORM_ROWS32, FORM_ROWS16, FORM_ROWS16_DIRECT, FORM_PER_GEMM, FORM_BF16_ANY = range(9)
 FORM_KERNELS = {FORM_UNPACKED: "ln_gemm_ng_kernel", FORM_SMALL: "sm_stack_kernel", FORM_TEAMS: "h2_stack_kernel<%d>", FORM_PAIRS: "h2_stack2_kernel<2>",
                 FORM_ROWS32: "h2_stackn_kernel<2>", FORM_ROWS16: "h2_stackn_kernel<2>", FORM_ROWS16_DIRECT: "h2_stackd_kernel<2>",
-                FORM_PER_GEMM: "h2_gemm_kernel"}
+                FORM_PER_GEMM: "h2_gemm_kernel", FORM_BF16_ANY: "b1a_gemm_kernel"}
+# mpl_bf16_operand_layout(): which packed bf16 operands the *_w16 fields of a stack shape carry (MPL_BF16_* of mpl_hip.h)
+BF16_NONE, BF16_TUNED, BF16_ANY = range(3)
 
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESIDUAL = 0, 1, 2
 
@@ -81,7 +83,7 @@ class Inputs(C.Structure):
 
 EXPORTS = ("mpl_hip_abi_version", "mpl_hip_error_string", "mpl_config_supported", "mpl_fpt_width", "mpl_forward_workspace_bytes",
            "mpl_forward", "mpl_spt_tokens", "mpl_block_stack_workspace_bytes", "mpl_block_stack", "mpl_block_stack_ex",
-           "mpl_ln_linear", "mpl_spt_pack_bytes", "mpl_spt_pack", "mpl_d32_pack", "mpl_pack_bf16_bytes", "mpl_pack_bf16", "mpl_pack_h2_bytes", "mpl_pack_h2", "mpl_pack_h2_scaled", "mpl_pack_h2_out_scale", "mpl_ln_linear_h2_workspace_bytes", "mpl_ln_linear_h2", "mpl_x3_debug_buffer", "mpl_x3_stack_mode", "mpl_block_stack_form", "mpl_block_stack_form_ex", "mpl_block_stack_last_form", "mpl_device_error", "mpl_device_error_clear", "mpl_x3_spin_limit", "mpl_token_attention", "mpl_fuse_head", "mpl_view_fuse", "mpl_view_norm",
+           "mpl_ln_linear", "mpl_spt_pack_bytes", "mpl_spt_pack", "mpl_d32_pack", "mpl_pack_bf16_bytes", "mpl_pack_bf16", "mpl_bf16_operand_layout", "mpl_pack_bf16_any_bytes", "mpl_pack_bf16_any", "mpl_ln_linear_bf16_any_workspace_bytes", "mpl_ln_linear_bf16_any", "mpl_pack_h2_bytes", "mpl_pack_h2", "mpl_pack_h2_scaled", "mpl_pack_h2_out_scale", "mpl_ln_linear_h2_workspace_bytes", "mpl_ln_linear_h2", "mpl_x3_debug_buffer", "mpl_x3_stack_mode", "mpl_block_stack_form", "mpl_block_stack_form_ex", "mpl_block_stack_last_form", "mpl_device_error", "mpl_device_error_clear", "mpl_x3_spin_limit", "mpl_token_attention", "mpl_fuse_head", "mpl_view_fuse", "mpl_view_norm",
            "mpl_layernorm", "mpl_linear", "mpl_pose_metrics_size", "mpl_pose_metrics", "mpl_pose_metrics_ex", "mpl_prepare_inputs", "mpl_profile_start",
            "mpl_profile_stop")
 KINDS = ("spt", "row_stats", "gemm", "attention", "fuse_head", "pack")
@@ -160,6 +162,17 @@ def load():
         lib.mpl_pack_bf16_bytes.argtypes = [C.c_int, C.c_int]
         lib.mpl_pack_bf16.restype = C.c_int
         lib.mpl_pack_bf16.argtypes = [_fp, _fp, _fp, _fp, C.c_int, C.c_int, _fp, _fp]
+        lib.mpl_bf16_operand_layout.restype = C.c_int
+        lib.mpl_bf16_operand_layout.argtypes = [C.c_int, C.c_int, C.c_int]
+        lib.mpl_pack_bf16_any_bytes.restype = C.c_size_t
+        lib.mpl_pack_bf16_any_bytes.argtypes = [C.c_int, C.c_int]
+        lib.mpl_pack_bf16_any.restype = C.c_int
+        lib.mpl_pack_bf16_any.argtypes = [_fp, _fp, _fp, _fp, C.c_int, C.c_int, _fp, _fp]
+        lib.mpl_ln_linear_bf16_any_workspace_bytes.restype = C.c_size_t
+        lib.mpl_ln_linear_bf16_any_workspace_bytes.argtypes = [C.c_int, C.c_int]
+        lib.mpl_ln_linear_bf16_any.restype = C.c_int
+        lib.mpl_ln_linear_bf16_any.argtypes = [_fp, C.c_int, C.c_int, C.c_int, C.c_float, _fp, C.c_int, C.c_int, _fp, _fp, _fp,
+                                               _fp, C.c_size_t, _fp]
         lib.mpl_pack_h2_bytes.restype = C.c_size_t
         lib.mpl_pack_h2_bytes.argtypes = [C.c_int, C.c_int]
         lib.mpl_pack_h2.restype = C.c_int

@@ -144,10 +144,30 @@ StackWs carve_stack_ws(void* base, size_t M, size_t D) {
 
 std::atomic<int> g_spin_log2{23};    // polls before a wait inside a persistent kernel counts as lost (mpl_x3_spin_limit)
 
-// 2 = every block carries fp16x2 operands (h2_gemm.hip, the default fp32 engine), 1 = packed bf16 operands (b1_gemm.hip), 0 = none
-// of them (or the shape has no packed layout): the stack then runs on the fp32 matrix instructions
+// THE rule for "which bf16 operand layout do the *_w16 fields of a stack of this shape carry" (mpl_bf16_operand_layout): the tuned
+// one of mpl_pack_bf16 where the team kernels take the shape (b1_gemm.hip), else the shape-general one of mpl_pack_bf16_any
+// (b1_any.hip: any width up to 4096, any head count that divides it, up to 32 tokens per sequence), else none
+int bf16_layout(int D, int H, int n_tok) {
+    if (D <= 0 || H <= 0 || n_tok <= 0) return MPL_E_INVALID;
+    // (D <= 1088: launch_pack_b1 / launch_b1_gemm combine at most 8 LayerNorm slice partials per row; wider multiples of 544 fall through)
+    if (D <= 1088 && h2_attention_fusable(n_tok, D, H) && h2_shape_ok(D, 2 * D)) return MPL_BF16_TUNED;
+    if (n_tok <= 32 && D % H == 0 && D <= 4096 && b1a_operand_bytes(3 * D, D) && b1a_operand_bytes(D, 2 * D)) return MPL_BF16_ANY;
+    return MPL_BF16_NONE;
+}
+
+// operand_parts of the engine a stack takes: 2 = every block carries fp16x2 operands (h2_gemm.hip, the default fp32 engine), 1 = packed
+// bf16 operands in the tuned layout (b1_gemm.hip), 3 = bf16 operands in the shape-general layout (b1_any.hip), 0 = none of them (or the
+// shape has no packed layout): the stack then runs on the fp32 matrix instructions.  `parts` = what the blocks carry (1 = *_w16).
+constexpr int NP_BF16_ANY = 3;
+int engine_parts(int parts, int n_tok, int D, int H) {
+    if (parts == 1) {
+        const int lay = bf16_layout(D, H, n_tok);
+        return lay == MPL_BF16_TUNED ? 1 : (lay == MPL_BF16_ANY ? NP_BF16_ANY : 0);
+    }
+    return (parts == 2 && h2_attention_fusable(n_tok, D, H) && h2_shape_ok(D, 2 * D)) ? 2 : 0;
+}
 int stack_packed_parts(const mpl_block_weights* blocks, const uint8_t* schedule, int n_apps, int n_tok, int D, int H) {
-    if (n_apps <= 0 || !h2_attention_fusable(n_tok, D, H) || !h2_shape_ok(D, 2 * D)) return 0;
+    if (n_apps <= 0) return 0;
     int np = 0;
     for (int a = 0; a < n_apps; ++a) {
         const mpl_block_weights& b = blocks[schedule[a]];
@@ -155,7 +175,49 @@ int stack_packed_parts(const mpl_block_weights* blocks, const uint8_t* schedule,
         if (bp == 0 || (np && bp != np)) return 0;
         np = bp;
     }
-    return np;
+    return engine_parts(np, n_tok, D, H);
+}
+
+// Workspace of the shape-general bf16 engine (b1_any.hip): x stays fp32 in place; qkv fp32 (the attention reads it), the attention
+// output and the GELU output as bf16 rows of leading dimension b1a_ld(width), the LayerNorm slice partials of launch_row_stats
+struct AnyWs {
+    float* qkv;
+    unsigned short *att, *hid;
+    float* stats;
+    size_t bytes;
+};
+AnyWs carve_any_ws(void* base, size_t M, size_t D) {
+    WsCarver c{reinterpret_cast<char*>(base)};
+    AnyWs w;
+    w.qkv = c.take<float>(M * 3 * D * sizeof(float));
+    w.att = c.take<unsigned short>(M * (size_t)b1a_ld((int)D) * 2);
+    w.hid = c.take<unsigned short>(M * (size_t)b1a_ld((int)(2 * D)) * 2);
+    w.stats = c.take<float>(M * 2 * (size_t)ln_stat_slices((int)D) * sizeof(float));
+    w.bytes = c.off;
+    return w;
+}
+
+// The block stack on the shape-general bf16 engine: per application a statistics pass, four GEMM launches and the token attention
+int block_stack_bf16_any(float* x, int n_seq, int n_tok, int D, int H, const mpl_block_weights* blocks, const uint8_t* schedule,
+                         int n_apps, void* ws, size_t ws_bytes, hipStream_t s) {
+    const int M = n_seq * n_tok, lda = b1a_ld(D), ldh = b1a_ld(2 * D);
+    const float eps = 1e-6f;  // norm_layer = partial(nn.LayerNorm, eps=1e-6), multiview_mpl.py:139
+    const AnyWs w = carve_any_ws(ws, (size_t)M, (size_t)D);
+    if (!ws || ws_bytes < w.bytes) return MPL_E_WORKSPACE;
+    int rc;
+    for (int a = 0; a < n_apps; ++a) {
+        const mpl_block_weights& b = blocks[schedule[a]];
+        // x = x + proj(attn(qkv(norm1(x))))   (Block.forward :84-90)
+        if ((rc = launch_row_stats(x, M, D, D, w.stats, s))) return rc;
+        if ((rc = launch_b1a_gemm(x, D, nullptr, 0, b.qkv_w16, w.stats, eps, nullptr, w.qkv, 3 * D, M, 3 * D, D, MPL_EPI_BIAS, s))) return rc;
+        if ((rc = launch_token_attention_bf16(w.qkv, n_seq, n_tok, D, H, w.att, lda, s))) return rc;
+        if ((rc = launch_b1a_gemm(nullptr, 0, w.att, lda, b.proj_w16, nullptr, 0.f, x, x, D, M, D, D, MPL_EPI_BIAS_RESIDUAL, s))) return rc;
+        // x = x + fc2(gelu(fc1(norm2(x))))    (Block.forward :91, Mlp.forward :31-37)
+        if ((rc = launch_row_stats(x, M, D, D, w.stats, s))) return rc;
+        if ((rc = launch_b1a_gemm(x, D, nullptr, 0, b.fc1_w16, w.stats, eps, nullptr, w.hid, ldh, M, 2 * D, D, MPL_EPI_BIAS_GELU, s))) return rc;
+        if ((rc = launch_b1a_gemm(nullptr, 0, w.hid, ldh, b.fc2_w16, nullptr, 0.f, x, x, D, M, D, 2 * D, MPL_EPI_BIAS_RESIDUAL, s))) return rc;
+    }
+    return MPL_OK;
 }
 
 // Workspace of the packed-operand engines.  x stays fp32 in place (residual stream, statistics); the attention output and the GELU
@@ -291,6 +353,11 @@ int block_stack_impl(float* x, int n_seq, int n_tok, int D, int H, const mpl_blo
             if (err_ws) *err_ws = nullptr;
         }
     }
+    if (np0 == NP_BF16_ANY) {
+        const int rc = block_stack_bf16_any(x, n_seq, n_tok, D, H, blocks, schedule, n_apps, ws, ws_bytes, s);
+        if (rc == MPL_OK) t_last_form = MPL_FORM_BF16_ANY;
+        return rc;
+    }
     if (const int np = np0) {
         const int rc = np == 2 ? block_stack_packed<2>(x, n_seq, n_tok, D, H, blocks, schedule, n_apps, ws, ws_bytes, err_ws, s)
                                : block_stack_packed<1>(x, n_seq, n_tok, D, H, blocks, schedule, n_apps, ws, ws_bytes, err_ws, s);
@@ -381,6 +448,10 @@ size_t stack_ws_bytes(size_t M, size_t D, int n_tok) {
         b = b2 > b ? b2 : b;
         const size_t b1 = carve_packed_ws(nullptr, M, D, rpt, 1).bytes;
         b = b1 > b ? b1 : b;
+    }
+    if (n_tok <= 32 && D <= 4096) {
+        const size_t ba = carve_any_ws(nullptr, M, D).bytes;
+        b = ba > b ? ba : b;
     }
     return b;
 }
@@ -539,6 +610,42 @@ int mpl_pack_bf16(const float* W, const float* bias, const float* ln_w, const fl
     return launch_pack_b1(W, N, K, ln_w, ln_b, bias, dst, (hipStream_t)stream);
 }
 
+int mpl_bf16_operand_layout(int dim, int heads, int n_tok) { return bf16_layout(dim, heads, n_tok); }
+
+size_t mpl_pack_bf16_any_bytes(int N, int K) { return b1a_operand_bytes(N, K); }
+
+int mpl_pack_bf16_any(const float* W, const float* bias, const float* ln_w, const float* ln_b, int N, int K, uint16_t* dst, void* stream) {
+    clear_stale_hip_error();
+    if (mpl_pack_bf16_any_bytes(N, K) == 0) return MPL_E_INVALID;
+    return launch_pack_b1a(W, N, K, ln_w, ln_b, bias, dst, (hipStream_t)stream);
+}
+
+size_t mpl_ln_linear_bf16_any_workspace_bytes(int M, int K) {
+    if (M <= 0 || K <= 0 || K > 8192) return 0;
+    return (size_t)M * b1a_ld(K) * 2;
+}
+
+int mpl_ln_linear_bf16_any(const float* x, int M, int K, int has_ln, float eps, const uint16_t* W16, int N, int epilogue,
+                           const float* residual, void* y, float* stats, void* workspace, size_t workspace_bytes, void* stream) {
+    clear_stale_hip_error();
+    if (!x || !W16 || !y || M <= 0 || b1a_operand_bytes(N, K) == 0) return MPL_E_INVALID;
+    if (!ln_gemm_rows_ok(M, K, K)) return MPL_E_UNSUPPORTED;        // the row envelope of the block stack (block_stack_impl)
+    hipStream_t s = (hipStream_t)stream;
+    int rc;
+    if (has_ln) {
+        if (!stats) return MPL_E_INVALID;
+        if (epilogue != MPL_EPI_BIAS && epilogue != MPL_EPI_BIAS_GELU) return MPL_E_UNSUPPORTED;
+        if ((rc = launch_row_stats(x, M, K, K, stats, s))) return rc;
+        return launch_b1a_gemm(x, K, nullptr, 0, W16, stats, eps, nullptr, y, N, M, N, K, epilogue, s);
+    }
+    if (epilogue != MPL_EPI_BIAS_RESIDUAL || !residual) return MPL_E_UNSUPPORTED;
+    if (!workspace || workspace_bytes < mpl_ln_linear_bf16_any_workspace_bytes(M, K)) return MPL_E_WORKSPACE;
+    if (reinterpret_cast<uintptr_t>(workspace) & 15) return MPL_E_INVALID;
+    unsigned short* a16 = reinterpret_cast<unsigned short*>(workspace);
+    if ((rc = launch_b1a_rows(x, M, K, a16, s))) return rc;
+    return launch_b1a_gemm(nullptr, 0, a16, b1a_ld(K), W16, nullptr, 0.f, residual, y, N, M, N, K, epilogue, s);
+}
+
 size_t mpl_pack_h2_bytes(int N, int K) { return h2_operand_bytes(N, K); }
 
 int mpl_pack_h2(const float* W, const float* bias, const float* ln_w, const float* ln_b, int N, int K, uint16_t* dst, void* stream) {
@@ -587,12 +694,13 @@ int mpl_block_stack_form_ex(int n_seq, int n_tok, int D, int heads, int n_apps, 
     if ((long long)n_seq * n_tok > (1ll << 30)) return MPL_E_UNSUPPORTED;
     const int M = n_seq * n_tok;
     // the same questions, in the same order, as block_stack_impl asks -- through the same predicates
-    const int np = (h2_attention_fusable(n_tok, D, heads) && h2_shape_ok(D, 2 * D)) ? operand_parts : 0;
+    const int np = engine_parts(operand_parts, n_tok, D, heads);
     int cus = 0;
     if (device_cu_count(&cus) != MPL_OK) return MPL_E_LAUNCH;
     if (M <= sm_stack_max_rows() && small_engine_taken(np, !(flags & MPL_F_NO_SMALL_STACK), M, D, n_tok, heads, n_apps, n_blocks, raw_tensors != 0, cus))
         return MPL_FORM_SMALL;
     if (np == 0) return MPL_FORM_UNPACKED;
+    if (np == NP_BF16_ANY) return MPL_FORM_BF16_ANY;
     if (g_stack_mode.load() & 1) return MPL_FORM_PER_GEMM;
     return h2_stack_form_code(M, D, n_tok, np, cus);
 }

@@ -253,6 +253,17 @@ int launch_b1_qkv_attention(const unsigned short* x16, const unsigned short* W1,
 int launch_b1_stack(float* x, unsigned short* x16, int M, int D, int n_tok, int heads, const unsigned short* const* ops, int n_apps,
                     unsigned short* att1, unsigned short* hid1, float* stats, unsigned* counters, float eps, int stop_after,
                     hipStream_t s);
+// Shape-general bf16 GEMMs (b1_any.hip): one plain launch per GEMM for run-time M, N, K; the operand of mpl_pack_bf16_any
+// ([ceil(N/64)][ceil(K/32)] fragment blocks of 4 KiB, zero padded, then fp32 c[N], s[N]).  X != nullptr: a LayerNorm GEMM on the raw
+// fp32 rows (stats: launch_row_stats partials; epi BIAS -> fp32 C, BIAS_GELU -> bf16 C); else a plain GEMM on the bf16 rows A16 of
+// leading dimension lda >= b1a_ld(K) (epi BIAS_RESIDUAL: C = R + ..., R may alias C).
+int b1a_ld(int K);                              // leading dimension of a bf16 activation matrix of width K (a multiple of 32)
+size_t b1a_operand_bytes(int N, int K);         // 0 = no layout (N outside 1..16384, K outside 1..8192)
+int launch_pack_b1a(const float* W, int N, int K, const float* ln_w, const float* ln_b, const float* bias, unsigned short* dst,
+                    hipStream_t s);
+int launch_b1a_rows(const float* X, int M, int K, unsigned short* dst, hipStream_t s);      // fp32 rows -> bf16 rows [M][b1a_ld(K)]
+int launch_b1a_gemm(const float* X, int ldx, const unsigned short* A16, int lda, const unsigned short* W16, const float* stats, float eps,
+                    const float* R, void* C, int ldc, int M, int N, int K, int epi, hipStream_t s);
 // Block stack for up to 80 token rows (sm_stack.hip; beyond one sequence: groups of sequences of at most 16 rows side by side): every GEMM on the whole chip (one 16-column tile per workgroup, weights
 // read in place), activations handed over as {value, tag} pairs, exact fp32 on the matrix cores
 bool sm_stack_ok(int M, int D, int n_tok, int H, int n_apps, int n_blocks, int cus);      // cus: every workgroup must be resident
@@ -261,6 +272,8 @@ int sm_stack_max_rows();
 int launch_sm_stack(float* x, int n_seq, int n_tok, int D, int H, const mpl_block_weights* blocks, const uint8_t* schedule, int n_apps,
                     void* ws, size_t ws_bytes, const unsigned** err_ws, int spin_log2, hipStream_t s);
 int launch_token_attention(const float* qkv, int n_seq, int n_tok, int dim, int heads, float* out, hipStream_t s);
+// the same (n_tok <= 32 only) with the output rounded to bf16 on the way out: out16 [n_seq * n_tok][ldo], columns >= dim untouched
+int launch_token_attention_bf16(const float* qkv, int n_seq, int n_tok, int dim, int heads, unsigned short* out16, int ldo, hipStream_t s);
 // use_packed: every SPT block carries the split operand of mpl_spt_pack in qkv_w3 (spt3_kernel: Linear layers on the bf16
 // matrix cores); else the fp32-MFMA kernel reads the nn.Linear weights in place
 int launch_spt(const mpl_config* cfg, const mpl_weights* w, const mpl_inputs* in, float* xs, int use_packed, hipStream_t s);

@@ -12,9 +12,20 @@
 
 namespace mpl {
 
-template <int VT>
-__global__ __launch_bounds__(256) void token_attention_kernel(const float* __restrict__ qkv, float* __restrict__ out,
-                                                               int n_seq, int n_tok, int D, int H, float scale) {
+// Store type of the short kernels (n_tok <= 32): fp32 rows of stride D, or -- for the shape-general bf16 engine (b1_any.hip), whose
+// proj GEMM takes the attention output as a bf16 operand -- bf16 (round to nearest even) rows of stride ldo, rounded on the way out.
+__device__ __forceinline__ void att_store4(float* p, const float4& v) { st4(p, v); }
+__device__ __forceinline__ void att_store4(unsigned short* p, const float4& v) {
+    typedef __bf16 att_bf4 __attribute__((ext_vector_type(4)));
+    const att_bf4 b = {(__bf16)v.x, (__bf16)v.y, (__bf16)v.z, (__bf16)v.w};
+    *reinterpret_cast<uint2*>(p) = __builtin_bit_cast(uint2, b);
+}
+__device__ __forceinline__ void att_store1(float* p, float v) { *p = v; }
+__device__ __forceinline__ void att_store1(unsigned short* p, float v) { *p = __builtin_bit_cast(unsigned short, (__bf16)v); }
+
+template <int VT, typename OT>
+__global__ __launch_bounds__(256) void token_attention_kernel(const float* __restrict__ qkv, OT* __restrict__ out,
+                                                               int n_seq, int n_tok, int D, int H, float scale, int ldo) {
     const int idx = blockIdx.x * 256 + threadIdx.x;
     const int total = n_seq * n_tok * H;
     if (idx >= total) return;
@@ -57,7 +68,7 @@ __global__ __launch_bounds__(256) void token_attention_kernel(const float* __res
 #pragma unroll
     for (int j = 0; j < VT; ++j) sc[j] *= inv;
 
-    float* o = out + ((size_t)sq * n_tok + i) * D + (size_t)h * hd;
+    OT* o = out + ((size_t)sq * n_tok + i) * ldo + (size_t)h * hd;
     const float* v0 = base + 2 * D;
     for (int e = 0; e < hd4; ++e) {
         float4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -71,7 +82,7 @@ __global__ __launch_bounds__(256) void token_attention_kernel(const float* __res
                 acc.w = fmaf(sc[j], vv.w, acc.w);
             }
         }
-        st4(o + 4 * e, acc);
+        att_store4(o + 4 * e, acc);
     }
 }
 
@@ -84,9 +95,10 @@ __global__ __launch_bounds__(256) void token_attention_kernel(const float* __res
 //   phase 2  one thread per (sequence, head, i):    softmax over j, in place
 //   phase 3  one thread per output float4:          o_i = sum_j p_ij v_j             -> global, coalesced
 // Rows are padded by 4 floats (3*D is a multiple of 32 banks, so unpadded rows of different tokens alias).
+template <typename OT>
 __global__ __launch_bounds__(256) void token_attention_lds_kernel(const float* __restrict__ qkv,
-                                                                   float* __restrict__ out, int n_seq, int n_tok,
-                                                                   int D, int H, float scale, int spw) {
+                                                                   OT* __restrict__ out, int n_seq, int n_tok,
+                                                                   int D, int H, float scale, int spw, int ldo) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int tid = threadIdx.x;
     const int seq0 = blockIdx.x * spw;
@@ -135,7 +147,7 @@ __global__ __launch_bounds__(256) void token_attention_lds_kernel(const float* _
     }
     __syncthreads();
     const int d4 = D >> 2;
-    float4* o4 = reinterpret_cast<float4*>(out + (size_t)seq0 * n_tok * D);
+    OT* orow = out + (size_t)seq0 * n_tok * ldo;
     for (int t = tid; t < rows * d4; t += 256) {
         const int c = t % d4, r = t / d4;          // r = s*n_tok + i
         const int h = (4 * c) / hd;
@@ -151,7 +163,7 @@ __global__ __launch_bounds__(256) void token_attention_lds_kernel(const float* _
             acc.z = fmaf(pj, vv.z, acc.z);
             acc.w = fmaf(pj, vv.w, acc.w);
         }
-        o4[t] = acc;
+        att_store4(orow + (size_t)r * ldo + 4 * c, acc);
     }
 }
 
@@ -439,9 +451,9 @@ __global__ __launch_bounds__(256) void token_attention_long_p4_kernel(const floa
 
 // The same for head dims that are not a multiple of 4 (FPT widths J*d of the shape-general models, e.g. hd = 17 at d = 2, H = 2):
 // scalar loads, one thread per (query row, head), up to 32 tokens.
-template <int VT>
-__global__ __launch_bounds__(256) void token_attention_any_kernel(const float* __restrict__ qkv, float* __restrict__ out, int n_seq,
-                                                                   int n_tok, int D, int H, float scale) {
+template <int VT, typename OT>
+__global__ __launch_bounds__(256) void token_attention_any_kernel(const float* __restrict__ qkv, OT* __restrict__ out, int n_seq,
+                                                                   int n_tok, int D, int H, float scale, int ldo) {
     const int idx = blockIdx.x * 256 + threadIdx.x;
     if (idx >= n_seq * n_tok * H) return;
     const int h = idx % H;
@@ -474,15 +486,65 @@ __global__ __launch_bounds__(256) void token_attention_any_kernel(const float* _
     const float inv = 1.0f / l;
 #pragma unroll
     for (int j = 0; j < VT; ++j) sc[j] *= inv;
-    float* o = out + ((size_t)sq * n_tok + i) * D + (size_t)h * hd;
+    OT* o = out + ((size_t)sq * n_tok + i) * ldo + (size_t)h * hd;
     const float* v0 = base + 2 * D;
     for (int e = 0; e < hd; ++e) {
         float acc = 0.f;
 #pragma unroll
         for (int j = 0; j < VT; ++j)
             if (j < n_tok) acc = fmaf(sc[j], v0[(size_t)j * ld + e], acc);
-        o[e] = acc;
+        att_store1(o + e, acc);
     }
+}
+
+// the short kernels (n_tok <= 32), any head dim, output type OT with row stride ldo
+template <typename OT>
+static int launch_short_attention(const float* qkv, int n_seq, int n_tok, int dim, int heads, OT* out, int ldo, hipStream_t s) {
+    const int hd = dim / heads;
+    const float scale = 1.0f / sqrtf((float)hd);
+    const long long total = (long long)n_seq * n_tok * heads;
+    if (total > 0x7fffffffll) return MPL_E_UNSUPPORTED;
+    ProfScope prof(MPL_K_ATTENTION, s);
+    if (hd & 3) {
+        const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+#define MPL_ATT(VT) hipLaunchKernelGGL((token_attention_any_kernel<VT, OT>), grid, block, 0, s, qkv, out, n_seq, n_tok, dim, heads, scale, ldo)
+        if (n_tok <= 4) MPL_ATT(4);
+        else if (n_tok <= 8) MPL_ATT(8);
+        else if (n_tok <= 16) MPL_ATT(16);
+        else MPL_ATT(32);
+#undef MPL_ATT
+        return hip_check_launch();
+    }
+    {
+        const size_t seq_bytes = (size_t)n_tok * (3 * dim + 4) * 4 + (size_t)heads * n_tok * n_tok * 4;
+        if (seq_bytes <= 150 * 1024) {
+            int spw = (int)((56 * 1024) / seq_bytes);
+            if (spw < 1) spw = 1;
+            if (spw > 8) spw = 8;
+            const size_t lds = spw * seq_bytes;
+            if (lds > 64 * 1024) {
+                if (int rc = kernel_lds_once<token_attention_lds_kernel<OT>>(150 * 1024)) return rc;
+            }
+            hipLaunchKernelGGL(token_attention_lds_kernel<OT>, dim3((n_seq + spw - 1) / spw), dim3(256), lds, s, qkv, out,
+                               n_seq, n_tok, dim, heads, scale, spw, ldo);
+            return hip_check_launch();
+        }
+    }
+    const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+#define MPL_ATT(VT) hipLaunchKernelGGL((token_attention_kernel<VT, OT>), grid, block, 0, s, qkv, out, n_seq, n_tok, dim, heads, scale, ldo)
+    if (n_tok <= 2) MPL_ATT(2);
+    else if (n_tok <= 4) MPL_ATT(4);
+    else if (n_tok <= 8) MPL_ATT(8);
+    else if (n_tok <= 16) MPL_ATT(16);
+    else MPL_ATT(32);
+#undef MPL_ATT
+    return hip_check_launch();
+}
+
+int launch_token_attention_bf16(const float* qkv, int n_seq, int n_tok, int dim, int heads, unsigned short* out16, int ldo, hipStream_t s) {
+    if (n_seq <= 0 || n_tok <= 0 || heads <= 0 || dim % heads || ldo < dim || (ldo & 3)) return MPL_E_INVALID;
+    if (n_tok > 32) return MPL_E_UNSUPPORTED;
+    return launch_short_attention(qkv, n_seq, n_tok, dim, heads, out16, ldo, s);
 }
 
 int launch_token_attention(const float* qkv, int n_seq, int n_tok, int dim, int heads, float* out, hipStream_t s) {
@@ -490,18 +552,7 @@ int launch_token_attention(const float* qkv, int n_seq, int n_tok, int dim, int 
     const int hd = dim / heads;
     if (hd & 3) {
         if (n_tok > 32) return MPL_E_UNSUPPORTED;
-        const float scale = 1.0f / sqrtf((float)hd);
-        const long long total = (long long)n_seq * n_tok * heads;
-        if (total > 0x7fffffffll) return MPL_E_UNSUPPORTED;
-        ProfScope prof(MPL_K_ATTENTION, s);
-        const dim3 grid((unsigned)((total + 255) / 256)), block(256);
-#define MPL_ATT(VT) hipLaunchKernelGGL((token_attention_any_kernel<VT>), grid, block, 0, s, qkv, out, n_seq, n_tok, dim, heads, scale)
-        if (n_tok <= 4) MPL_ATT(4);
-        else if (n_tok <= 8) MPL_ATT(8);
-        else if (n_tok <= 16) MPL_ATT(16);
-        else MPL_ATT(32);
-#undef MPL_ATT
-        return hip_check_launch();
+        return launch_short_attention(qkv, n_seq, n_tok, dim, heads, out, dim, s);
     }
     if (n_tok > 32) {
         if ((hd != 4 && hd != 8) || (size_t)n_tok * hd * 8 > 64 * 1024) return MPL_E_UNSUPPORTED;
@@ -526,33 +577,7 @@ int launch_token_attention(const float* qkv, int n_seq, int n_tok, int dim, int 
                                dim, heads, sc);
         return hip_check_launch();
     }
-    const float scale = 1.0f / sqrtf((float)hd);
-    const int total = n_seq * n_tok * heads;
-    ProfScope prof(MPL_K_ATTENTION, s);
-    {
-        const size_t seq_bytes = (size_t)n_tok * (3 * dim + 4) * 4 + (size_t)heads * n_tok * n_tok * 4;
-        if (seq_bytes <= 150 * 1024) {
-            int spw = (int)((56 * 1024) / seq_bytes);
-            if (spw < 1) spw = 1;
-            if (spw > 8) spw = 8;
-            const size_t lds = spw * seq_bytes;
-            if (lds > 64 * 1024) {
-                if (int rc = kernel_lds_once<token_attention_lds_kernel>(150 * 1024)) return rc;
-            }
-            hipLaunchKernelGGL(token_attention_lds_kernel, dim3((n_seq + spw - 1) / spw), dim3(256), lds, s, qkv, out,
-                               n_seq, n_tok, dim, heads, scale, spw);
-            return hip_check_launch();
-        }
-    }
-    const dim3 grid((total + 255) / 256), block(256);
-#define MPL_ATT(VT) hipLaunchKernelGGL((token_attention_kernel<VT>), grid, block, 0, s, qkv, out, n_seq, n_tok, dim, heads, scale)
-    if (n_tok <= 2) MPL_ATT(2);
-    else if (n_tok <= 4) MPL_ATT(4);
-    else if (n_tok <= 8) MPL_ATT(8);
-    else if (n_tok <= 16) MPL_ATT(16);
-    else MPL_ATT(32);
-#undef MPL_ATT
-    return hip_check_launch();
+    return launch_short_attention(qkv, n_seq, n_tok, dim, heads, out, dim, s);
 }
 
 }  // namespace mpl

@@ -361,14 +361,21 @@ class MultiView_MPL(nn.Module):
             exact power-of-two scales, three partial products per product (csrc/h2_gemm.hip: as accurate as an fp32 GEMM,
             1/5 of its matrix-pipe time on gfx950); other widths (KPTOK, D = 32) use the native fp32 MFMA kernels;
         "fp32_mfma" -- native fp32 matrix instructions (v_mfma_f32_16x16x4_f32) everywhere;
-        "bf16" -- the same stage with ONE bf16 per operand element (csrc/b1_gemm.hip): operands rounded to bf16 (activations
-            when a GEMM epilogue hands them to the next GEMM, weights with the LayerNorm gain folded in), exact products, fp32
-            accumulation; statistics, softmax, GELU and the residual stream stay fp32: BASELINE.json configs[2].
+        "bf16" -- the FPT GEMMs with ONE bf16 per operand element: operands rounded to bf16 (activations when they are handed
+            to the next GEMM, weights with the LayerNorm gain folded in), exact products, fp32 accumulation; statistics,
+            softmax, GELU and the residual stream stay fp32: BASELINE.json configs[2].  Every view-token model runs it
+            (input_rays_as_token and no_transformer_spt included, 1 .. 32 views): widths 544 / 1088 with a head that tiles a
+            136-column slice on the team kernels (csrc/b1_gemm.hip), every other width, DIM and head count on the shape-general
+            kernel (csrc/b1_any.hip, one launch per GEMM) -- the library decides (mpl_bf16_operand_layout).  Out of scope, they
+            raise NotImplementedError: the joints x views token grid (FPT_blocks_view_keypoint_tokens: GEMMs of K <= 128 in an
+            attention-bound stage, bf16 buys nothing) and models without FPT blocks (no_transformer_fpt / depth 0: nothing to run).
         The packed weight copies are derived data, rebuilt whenever a parameter's storage or version changes."""
         if precision not in ("fp32", "fp32_mfma", "bf16"):
             raise ValueError("matmul precision must be 'fp32', 'fp32_mfma' or 'bf16'")
-        if precision == "bf16" and not self._x3_supported():
-            raise NotImplementedError("the %s engine covers the view-token FPT blocks (widths 544 / 1088, up to 32 views)" % precision)
+        if precision == "bf16" and self._bf16_layout() == cabi.BF16_NONE:
+            raise NotImplementedError("the bf16 engine covers the view-token FPT blocks (any width up to 4096, up to 32 views); the "
+                                      "joints x views token grid (FPT_blocks_view_keypoint_tokens) and models without FPT blocks "
+                                      "(no_transformer_fpt / depth 0) have none")
         self.matmul_precision = precision
         self._drop_caches()
         return self
@@ -393,6 +400,14 @@ class MultiView_MPL(nn.Module):
                      for t in (b.attn.qkv.weight, b.attn.proj.weight, b.mlp.fc1.weight, b.mlp.fc2.weight))
         self.__dict__["_x3_ok"] = (_STRUCT_GEN[0], ok)
         return ok
+
+    def _bf16_layout(self) -> int:
+        """cabi.BF16_TUNED / BF16_ANY: the packed bf16 operands the FPT blocks of this model carry under "bf16" (the library's
+        rule, mpl_bf16_operand_layout: the same one mpl_block_stack launches by); BF16_NONE: no bf16 engine for this model."""
+        if self.no_transformer_fpt or len(self.blocks) == 0 or self.FPT_blocks_view_keypoint_tokens:
+            return cabi.BF16_NONE
+        D = int(self.blocks[0].attn.qkv.weight.shape[1])
+        return max(cabi.BF16_NONE, cabi.load().mpl_bf16_operand_layout(D, self.num_heads, self.num_views))
 
     def _tensor_lists(self):
         """(every tensor handed to the library, the tensors of the FPT blocks, the tensors of the SPT blocks) of THIS module,
@@ -530,7 +545,8 @@ class MultiView_MPL(nn.Module):
         as long as the tensors they were built from keep their storage and version (_derived_key)."""
         plist = self._tensor_lists()[0]
         x3ok = self._x3_supported()
-        bf16 = self.matmul_precision == "bf16" and x3ok
+        bf16_lay = self._bf16_layout() if self.matmul_precision == "bf16" else cabi.BF16_NONE
+        bf16 = bf16_lay != cabi.BF16_NONE
         h2 = self.matmul_precision == "fp32" and x3ok
         # the SPT Linear layers also run from split operands (fp32 arithmetic on the fp16 matrix cores) unless the native
         # fp32 matrix instructions were asked for
@@ -595,7 +611,7 @@ class MultiView_MPL(nn.Module):
             if bf16 or h2:
                 ops = derived["fpt"].get(l)
                 if ops is None:
-                    ops = self._pack_block(lib, b, device, st, bf16)
+                    ops = self._pack_block(lib, b, device, st, bf16, bf16_lay == cabi.BF16_ANY)
                     derived["fpt"][l] = ops
                 if h2:
                     ptrs += [0] * 8           # behind the *_w16 and *_w3 fields
@@ -700,10 +716,13 @@ class MultiView_MPL(nn.Module):
         return out
 
     @staticmethod
-    def _pack_block(lib, b, device, st, bf16):
-        """The four packed Linear operands {qkv (norm1 folded), proj, fc1 (norm2 folded), fc2} of one FPT block."""
+    def _pack_block(lib, b, device, st, bf16, bf16_any=False):
+        """The four packed Linear operands {qkv (norm1 folded), proj, fc1 (norm2 folded), fc2} of one FPT block.  bf16_any: the
+        shape-general bf16 layout (mpl_pack_bf16_any) instead of the tuned one."""
         h2 = not bf16
         nbytes, pack = (lib.mpl_pack_bf16_bytes, lib.mpl_pack_bf16) if bf16 else (lib.mpl_pack_h2_bytes, lib.mpl_pack_h2)
+        if bf16 and bf16_any:
+            nbytes, pack = lib.mpl_pack_bf16_any_bytes, lib.mpl_pack_bf16_any
         ops = []
         in_scale = 0        # h2: static scales (device vector) of the columns the NEXT plain Linear consumes
         for lin, ln in ((b.attn.qkv, b.norm1), (b.attn.proj, None), (b.mlp.fc1, b.norm2), (b.mlp.fc2, None)):

@@ -1,6 +1,9 @@
 """poses/s of models outside NUM_JOINTS 17 / DIM 32 / HEADS 8 (and of 17 / 32 / 8 on the shape-general SPT next to the tuned one).
 
-    python tools/shape_bench.py [--batch 1024] [--views 4] [--depth 12] [--precision fp32]
+    python tools/shape_bench.py [--batch 1024] [--views 4] [--depth 12] [--precision fp32 [bf16 ...]]
+
+--precision takes one or more of fp32 / fp32_mfma / bf16; with several, every shape is measured under each in turn (the precisions
+alternate shape by shape, so that they share the box's clock and thermal state).
 
 One mpl_forward per step through the C ABI on the model's marshalled weights (the ctypes route of MultiView_MPL.forward), flags
 CHOSEN; poses/s = median over 5 timed regions of 20 forwards each (bench.py's secondary numbers), after 10 warm-up forwards.  Each
@@ -76,14 +79,15 @@ def main():
     ap.add_argument("--batch", type=int, default=1024)
     ap.add_argument("--views", type=int, default=4)
     ap.add_argument("--depth", type=int, default=12)
-    ap.add_argument("--precision", default="fp32", choices=("fp32", "fp32_mfma"))
+    ap.add_argument("--precision", nargs="+", default=["fp32"], choices=("fp32", "fp32_mfma", "bf16"))
     ap.add_argument("--only", default=None, help="one shape name")
     a = ap.parse_args()
     for name, J, d, H, extra in SHAPES:
         if a.only and name != a.only:
             continue
-        r = measure(J, d, H, extra, a.batch, a.views, a.depth, a.precision)
-        print(json.dumps(dict(shape=name, batch=a.batch, views=a.views, depth=a.depth, precision=a.precision, **r)), flush=True)
+        for prec in a.precision:
+            r = measure(J, d, H, extra, a.batch, a.views, a.depth, prec)
+            print(json.dumps(dict(shape=name, batch=a.batch, views=a.views, depth=a.depth, precision=prec, **r)), flush=True)
 
 
 if __name__ == "__main__":
