@@ -166,8 +166,9 @@ const char *mpl_hip_error_string(int code);
  *   FPT width J*d (x2 with MPL_F_RAYS_TOKEN) <= 4096;  1 <= num_views <= MPL_MAX_VIEWS;  depth 0..60 (0..31 with
  *   MPL_F_CONF_ATTN_W: every SPT block then runs twice);
  *   MPL_F_POS3D_TO_RAYS only with MPL_F_RAYS_TOKEN and not with MPL_F_POS3D_SPATIAL (the reference fails, :483);
- *   MPL_F_KPTOK (FPT blocks over J*V tokens of width d): not with MPL_F_RAYS_TOKEN; up to 32 tokens any head dim, more tokens
- *   need head dim 4 or 8 and J*V*hd*8 <= 64 KiB (K / V of one head resident in LDS). */
+ *   MPL_F_KPTOK (FPT blocks over J*V tokens of width d): not with MPL_F_RAYS_TOKEN; up to 32 tokens any head dim; more tokens
+ *   need head dim 4 or 8 with J*V*hd*8 <= 64 KiB (K / V of one head resident in LDS), or a head dim that is a multiple of 16 up to
+ *   128 with J*V <= 2048 (K / V streamed through LDS, token_attention_wide.hip).  Any other head dim beyond 32 tokens is refused. */
 int mpl_config_supported(const mpl_config *cfg);
 
 /* FPT token width D_f = J*d (x2 with MPL_F_RAYS_TOKEN), multiview_mpl.py:140-142. */
@@ -299,7 +300,9 @@ int mpl_block_stack_form_ex(int n_seq, int n_tok, int D, int heads, int n_apps, 
  * the fall-through when the small-batch engine's occupancy query refuses); negative before the first one. */
 int mpl_block_stack_last_form(void);
 
-/* softmax(q k^T * hd^-0.5) v per (sequence, head) on a packed qkv (n_seq*n_tok, 3*dim). Attention :55-64. */
+/* softmax(q k^T * hd^-0.5) v per (sequence, head) on a packed qkv (n_seq*n_tok, 3*dim). Attention :55-64.
+ * n_tok <= 32: any head dim.  Beyond: head dim 4 or 8 with n_tok*hd*8 <= 64 KiB, or a multiple of 16 up to 128 with n_tok <= 2048;
+ * anything else answers MPL_E_UNSUPPORTED and launches nothing. */
 int mpl_token_attention(const float *qkv, int n_seq, int n_tok, int dim, int heads, float *out, void *stream);
 
 /* Stage 3: strip ray features, View_norm, Conv1d weighted mean over views, head LN + Linear.

@@ -463,10 +463,7 @@ int check_cfg(const mpl_config* cfg) {
 }
 
 // the joints x views token grid of a keypoint-token FPT: the attention kernels that take it (launch_token_attention)
-bool kptok_attention_ok(int n_tok, int hd) {
-    if (n_tok <= 32) return true;                                  // short attention: any head dim
-    return (hd == 4 || hd == 8) && (size_t)n_tok * hd * 8 <= 64 * 1024;
-}
+bool kptok_attention_ok(int n_tok, int hd) { return token_attention_ok(n_tok, hd); }
 
 }  // namespace
 

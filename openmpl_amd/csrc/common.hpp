@@ -272,6 +272,13 @@ int sm_stack_max_rows();
 int launch_sm_stack(float* x, int n_seq, int n_tok, int D, int H, const mpl_block_weights* blocks, const uint8_t* schedule, int n_apps,
                     void* ws, size_t ws_bytes, const unsigned** err_ws, int spin_log2, hipStream_t s);
 int launch_token_attention(const float* qkv, int n_seq, int n_tok, int dim, int heads, float* out, hipStream_t s);
+// THE rule for "launch_token_attention takes n_tok tokens of head dim hd": up to 32 tokens any head dim (the short kernels); beyond,
+// hd 4 / 8 with K and V of a head in 64 KiB of LDS (the long kernels), or hd a multiple of 16 up to 128 with at most 2048 tokens
+// (token_attention_wide.hip).  The launcher dispatches by it, mpl_config_supported answers for the joints x views grid by it.
+bool token_attention_ok(int n_tok, int hd);
+// the streaming kernel for wide heads (token_attention_wide.hip): n_tok 33 .. 2048, hd % 16 == 0, hd <= 128
+bool token_attention_wide_ok(int n_tok, int hd);
+int launch_token_attention_wide(const float* qkv, int n_seq, int n_tok, int dim, int heads, float* out, hipStream_t s);
 // the same (n_tok <= 32 only) with the output rounded to bf16 on the way out: out16 [n_seq * n_tok][ldo], columns >= dim untouched
 int launch_token_attention_bf16(const float* qkv, int n_seq, int n_tok, int dim, int heads, unsigned short* out16, int ldo, hipStream_t s);
 // use_packed: every SPT block carries the split operand of mpl_spt_pack in qkv_w3 (spt3_kernel: Linear layers on the bf16

@@ -547,15 +547,22 @@ int launch_token_attention_bf16(const float* qkv, int n_seq, int n_tok, int dim,
     return launch_short_attention(qkv, n_seq, n_tok, dim, heads, out16, ldo, s);
 }
 
+// the long kernels above: K and V of one head resident in 64 KiB of LDS
+static bool long_resident_ok(int n_tok, int hd) { return n_tok > 32 && (hd == 4 || hd == 8) && (size_t)n_tok * hd * 8 <= 64 * 1024; }
+
+bool token_attention_ok(int n_tok, int hd) {
+    if (n_tok < 1 || hd < 1) return false;
+    return n_tok <= 32 || long_resident_ok(n_tok, hd) || token_attention_wide_ok(n_tok, hd);
+}
+
 int launch_token_attention(const float* qkv, int n_seq, int n_tok, int dim, int heads, float* out, hipStream_t s) {
     if (n_seq <= 0 || n_tok <= 0 || heads <= 0 || dim % heads) return MPL_E_INVALID;
     const int hd = dim / heads;
-    if (hd & 3) {
-        if (n_tok > 32) return MPL_E_UNSUPPORTED;
-        return launch_short_attention(qkv, n_seq, n_tok, dim, heads, out, dim, s);
-    }
+    if (!token_attention_ok(n_tok, hd)) return MPL_E_UNSUPPORTED;
+    if (hd & 3) return launch_short_attention(qkv, n_seq, n_tok, dim, heads, out, dim, s);
     if (n_tok > 32) {
-        if ((hd != 4 && hd != 8) || (size_t)n_tok * hd * 8 > 64 * 1024) return MPL_E_UNSUPPORTED;
+        // wide heads (hd a multiple of 16): K / V streamed through LDS, both products on the fp32 matrix cores
+        if (!long_resident_ok(n_tok, hd)) return launch_token_attention_wide(qkv, n_seq, n_tok, dim, heads, out, s);
         const float sc = 1.0f / sqrtf((float)hd);
         ProfScope prof(MPL_K_ATTENTION, s);
         const size_t lds = (size_t)n_tok * hd * 8;

@@ -340,11 +340,11 @@ class MultiView_MPL(nn.Module):
             reason = "depth > 31 with confidence_as_attention_uncertainty_weight (SPT schedule longer than %d blocks)" % cabi.MPL_MAX_APPS
         elif self.FPT_blocks_view_keypoint_tokens and self.input_rays_as_token:
             reason = "FPT_blocks_view_keypoint_tokens with input_rays_as_token (the reference itself fails: LN(d) on 2d)"
-        elif kp_fpt and J * V > 32 and hd not in (4, 8):
-            reason = ("joints x views grid of %d tokens (> 32) needs head dim 4 or 8 for the long token attention (head dim %d)"
-                      % (J * V, hd))
-        elif kp_fpt and J * V > 32 and J * V * hd * 8 > 64 * 1024:
-            reason = "joints x views grid too long for the LDS-resident K/V of one head"
+        elif kp_fpt and J * V > 32 and hd not in (4, 8) and hd % 16:      # (hd <= DIM <= 128 here)
+            reason = ("joints x views grid of %d tokens (> 32) needs head dim 4 or 8, or a multiple of 16 up to 128, for the long "
+                      "token attention (head dim %d)" % (J * V, hd))
+        elif kp_fpt and J * V > 32 and hd in (4, 8) and J * V * hd * 8 > 64 * 1024:
+            reason = "joints x views grid too long for the LDS-resident K/V of one head (head dim 4 or 8)"
         elif self.add_3D_pos_encoding_to_rays and not self.input_rays_as_token:
             reason = "add_3D_pos_encoding_to_rays without input_rays_as_token (the reference itself fails, :483)"
         elif self.add_3D_pos_encoding_to_rays and self.add_3D_pos_encoding_in_Spatial:
@@ -359,7 +359,11 @@ class MultiView_MPL(nn.Module):
         "fp32" (default) -- fp32 in, fp32 out, fp32 accumulation; where the FPT width is a multiple of 136 (every
             view-token model) the products are formed on the fp16 matrix cores from operands split into two fp16 terms under
             exact power-of-two scales, three partial products per product (csrc/h2_gemm.hip: as accurate as an fp32 GEMM,
-            1/5 of its matrix-pipe time on gfx950); other widths (KPTOK, D = 32) use the native fp32 MFMA kernels;
+            1/5 of its matrix-pipe time on gfx950); other widths (KPTOK, D = 32) use the native fp32 MFMA kernels.  The joints x
+            views token grid (FPT_blocks_view_keypoint_tokens) attends over NUM_JOINTS x views tokens in fp32 under "fp32" and
+            "fp32_mfma" alike: up to 32 tokens any head dim; beyond, head dim 4 or 8 (K / V of a head resident in LDS) or a
+            multiple of 16 up to 128 (K / V streamed, both products on v_mfma_f32_16x16x4_f32, csrc/token_attention_wide.hip).
+            Any other head dim beyond 32 tokens raises NotImplementedError;
         "fp32_mfma" -- native fp32 matrix instructions (v_mfma_f32_16x16x4_f32) everywhere;
         "bf16" -- the FPT GEMMs with ONE bf16 per operand element: operands rounded to bf16 (activations when they are handed
             to the next GEMM, weights with the LayerNorm gain folded in), exact products, fp32 accumulation; statistics,
