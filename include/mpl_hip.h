@@ -300,6 +300,20 @@ int mpl_block_stack_form_ex(int n_seq, int n_tok, int D, int heads, int n_apps, 
  * the fall-through when the small-batch engine's occupancy query refuses); negative before the first one. */
 int mpl_block_stack_last_form(void);
 
+/* Which kernel the SPT stage (mpl_spt_tokens, mpl_forward) launches for `batch` poses and how many sequences (one pose in one
+ * view) share a workgroup, by the library's own rule (csrc/spt.hip spt_form: both launchers follow it).  The smallest c with
+ * num_views * ceil(batch / c) <= compute units, at most 16 (tuned kernels, J 17 / d 32 / H 8) or what fits 64 KiB of LDS
+ * (shape-general kernel).  use_packed != 0: the SPT blocks carry mpl_spt_pack operands (mpl_weights.spt_packed). */
+enum {
+    MPL_SPT_STAGED = 0,           /* spt_kernel<true>: fp32 MFMA, weights staged in LDS, up to 8 sequences per workgroup */
+    MPL_SPT_FRAGS = 1,            /* spt_kernel<false>: weight fragments in registers, 9 .. 16 sequences per workgroup */
+    MPL_SPT_PACKED = 2,           /* spt3_kernel<SS>: split operands, SS = 1, 2, 4, 8 or 16 sequences per workgroup */
+    MPL_SPT_ANY = 3               /* spt_any_kernel: every other shape, and 17 / 32 / 8 with MPL_F_GENERIC_SPT */
+};
+/* kernel the SPT launch for `batch` poses takes and its sequences per workgroup (*seq_per_wg; SS for MPL_SPT_PACKED);
+ * n_cus <= 0: ask the current device.  Launches nothing.  Negative = MPL_E_*. */
+int mpl_spt_form(const mpl_config *cfg, int batch, int use_packed, int n_cus, int *seq_per_wg);
+
 /* softmax(q k^T * hd^-0.5) v per (sequence, head) on a packed qkv (n_seq*n_tok, 3*dim). Attention :55-64.
  * n_tok <= 32: any head dim.  Beyond: head dim 4 or 8 with n_tok*hd*8 <= 64 KiB, or a multiple of 16 up to 128 with n_tok <= 2048;
  * anything else answers MPL_E_UNSUPPORTED and launches nothing. */

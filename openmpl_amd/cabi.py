@@ -36,6 +36,9 @@ FORM_UNPACKED, FORM_SMALL, FORM_TEAMS, FORM_PAIRS, FORM_ROWS32, FORM_ROWS16, FOR
 FORM_KERNELS = {FORM_UNPACKED: "ln_gemm_ng_kernel", FORM_SMALL: "sm_stack_kernel", FORM_TEAMS: "h2_stack_kernel<%d>", FORM_PAIRS: "h2_stack2_kernel<2>",
                 FORM_ROWS32: "h2_stackn_kernel<2>", FORM_ROWS16: "h2_stackn_kernel<2>", FORM_ROWS16_DIRECT: "h2_stackd_kernel<2>",
                 FORM_PER_GEMM: "h2_gemm_kernel", FORM_BF16_ANY: "b1a_gemm_kernel"}
+# mpl_spt_form(): the kernel an SPT launch takes (MPL_SPT_* of mpl_hip.h)
+SPT_STAGED, SPT_FRAGS, SPT_PACKED, SPT_ANY = range(4)
+SPT_KERNELS = {SPT_STAGED: "spt_kernel<true>", SPT_FRAGS: "spt_kernel<false>", SPT_PACKED: "spt3_kernel<%d>", SPT_ANY: "spt_any_kernel"}
 # mpl_bf16_operand_layout(): which packed bf16 operands the *_w16 fields of a stack shape carry (MPL_BF16_* of mpl_hip.h)
 BF16_NONE, BF16_TUNED, BF16_ANY = range(3)
 
@@ -83,7 +86,7 @@ class Inputs(C.Structure):
 
 EXPORTS = ("mpl_hip_abi_version", "mpl_hip_error_string", "mpl_config_supported", "mpl_fpt_width", "mpl_forward_workspace_bytes",
            "mpl_forward", "mpl_spt_tokens", "mpl_block_stack_workspace_bytes", "mpl_block_stack", "mpl_block_stack_ex",
-           "mpl_ln_linear", "mpl_spt_pack_bytes", "mpl_spt_pack", "mpl_d32_pack", "mpl_pack_bf16_bytes", "mpl_pack_bf16", "mpl_bf16_operand_layout", "mpl_pack_bf16_any_bytes", "mpl_pack_bf16_any", "mpl_ln_linear_bf16_any_workspace_bytes", "mpl_ln_linear_bf16_any", "mpl_pack_h2_bytes", "mpl_pack_h2", "mpl_pack_h2_scaled", "mpl_pack_h2_out_scale", "mpl_ln_linear_h2_workspace_bytes", "mpl_ln_linear_h2", "mpl_x3_debug_buffer", "mpl_x3_stack_mode", "mpl_block_stack_form", "mpl_block_stack_form_ex", "mpl_block_stack_last_form", "mpl_device_error", "mpl_device_error_clear", "mpl_x3_spin_limit", "mpl_token_attention", "mpl_fuse_head", "mpl_view_fuse", "mpl_view_norm",
+           "mpl_ln_linear", "mpl_spt_pack_bytes", "mpl_spt_pack", "mpl_d32_pack", "mpl_pack_bf16_bytes", "mpl_pack_bf16", "mpl_bf16_operand_layout", "mpl_pack_bf16_any_bytes", "mpl_pack_bf16_any", "mpl_ln_linear_bf16_any_workspace_bytes", "mpl_ln_linear_bf16_any", "mpl_pack_h2_bytes", "mpl_pack_h2", "mpl_pack_h2_scaled", "mpl_pack_h2_out_scale", "mpl_ln_linear_h2_workspace_bytes", "mpl_ln_linear_h2", "mpl_x3_debug_buffer", "mpl_x3_stack_mode", "mpl_block_stack_form", "mpl_block_stack_form_ex", "mpl_block_stack_last_form", "mpl_spt_form", "mpl_device_error", "mpl_device_error_clear", "mpl_x3_spin_limit", "mpl_token_attention", "mpl_fuse_head", "mpl_view_fuse", "mpl_view_norm",
            "mpl_layernorm", "mpl_linear", "mpl_pose_metrics_size", "mpl_pose_metrics", "mpl_pose_metrics_ex", "mpl_prepare_inputs", "mpl_profile_start",
            "mpl_profile_stop")
 KINDS = ("spt", "row_stats", "gemm", "attention", "fuse_head", "pack")
@@ -194,6 +197,8 @@ def load():
         lib.mpl_block_stack_form_ex.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint]
         lib.mpl_block_stack_last_form.restype = C.c_int
         lib.mpl_block_stack_last_form.argtypes = []
+        lib.mpl_spt_form.restype = C.c_int
+        lib.mpl_spt_form.argtypes = [C.POINTER(Config), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
         for fn in (lib.mpl_device_error, lib.mpl_device_error_clear, lib.mpl_x3_spin_limit):
             fn.restype = C.c_int
             fn.argtypes = [C.c_int]

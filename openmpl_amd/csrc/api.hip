@@ -709,6 +709,18 @@ int mpl_block_stack_form(int n_seq, int n_tok, int D, int heads, int n_apps, int
 
 int mpl_block_stack_last_form(void) { return t_last_form; }
 
+int mpl_spt_form(const mpl_config* cfg, int batch, int use_packed, int n_cus, int* seq_per_wg) {
+    int rc = check_cfg(cfg);
+    if (rc) return rc;
+    if ((rc = mpl_config_supported(cfg))) return rc;
+    if (batch <= 0) return MPL_E_INVALID;
+    if (n_cus <= 0 && (rc = spt_device_cus(&n_cus))) return rc;
+    int spw = 0;
+    rc = spt_form(cfg, batch, use_packed, n_cus, &spw);
+    if (rc >= 0 && seq_per_wg) *seq_per_wg = spw;
+    return rc;
+}
+
 int mpl_x3_stack_mode(int one_launch_per_gemm) {
     g_stack_mode.store(one_launch_per_gemm);      // the bits: common.hpp stack_mode()
     return MPL_OK;

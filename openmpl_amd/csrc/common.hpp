@@ -286,6 +286,12 @@ int launch_token_attention_bf16(const float* qkv, int n_seq, int n_tok, int dim,
 int launch_spt(const mpl_config* cfg, const mpl_weights* w, const mpl_inputs* in, float* xs, int use_packed, hipStream_t s);
 // any J / d / H inside mpl_config_supported (spt_any.hip): fp32 FMA, the nn.Linear weights read in place
 int launch_spt_any(const mpl_config* cfg, const mpl_weights* w, const mpl_inputs* in, float* xs, hipStream_t s);
+// THE rule for the kernel (MPL_SPT_* of mpl_hip.h) and the sequences per workgroup (*spw; SS of spt3_kernel<SS> for MPL_SPT_PACKED)
+// an SPT launch for `batch` poses takes on a device of `cus` compute units (spt.hip): both launchers follow it, mpl_spt_form reports it
+int spt_form(const mpl_config* cfg, int batch, int use_packed, int cus, int* spw);
+int spt_device_cus(int* cus);
+size_t spt_any_row_bytes(int d);
+int spt_any_seq_cap(int J, int d);
 size_t spt_pack_bytes();
 int launch_spt_pack(const mpl_block_weights* bw_host, unsigned short* dst, int fold_q, hipStream_t s);
 int launch_d32_qkv(const float* x, int M, const unsigned short* pack, float* qkv, hipStream_t s);

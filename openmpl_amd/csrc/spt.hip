@@ -1347,10 +1347,50 @@ int launch_d32_mlp(float* x, const float* att, int M, const unsigned short* pack
     return hip_check_launch();
 }
 
+// compute units of the current device (asked once per device)
+int spt_device_cus(int* cus) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return MPL_E_LAUNCH;
+    static std::atomic<int> n_cus[64];
+    *cus = n_cus[dev].load(std::memory_order_acquire);
+    if (*cus == 0) {
+        if (hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || *cus < 1) return MPL_E_LAUNCH;
+        n_cus[dev].store(*cus, std::memory_order_release);
+    }
+    return MPL_OK;
+}
+
+// every other shape, and 17 / 32 / 8 on request, runs on the shape-general kernel (spt_any.hip)
+static bool spt_shape_general(const mpl_config* cfg) {
+    return cfg->num_joints != SJ || cfg->dim != SD || cfg->heads != SH || (cfg->flags & MPL_F_GENERIC_SPT);
+}
+
+// THE rule by which an SPT launch picks its kernel and its sequences per workgroup: launch_spt and launch_spt_any launch by it,
+// mpl_spt_form reports by it.  As few sequences per workgroup as keep the launch inside one wave of workgroups (one per CU), so
+// that a single frame or a few hundred sequences use the whole chip with 2-3 live row tiles per workgroup instead of a few
+// workgroups with 17: the smallest c with V ceil(B / c) <= cus, at most SEQ for the tuned kernels and spt_any_seq_cap (LDS) for
+// the shape-general one.  Tuned, nn.Linear weights: up to SPT_SMALL_SPW per workgroup run the staged form (spt_kernel<true>),
+// more the fragment form.  Tuned, packed operands: 16, 8, 4, 2 or 1 sequences per workgroup, the next power of two (bitwise the
+// same rows).
+int spt_form(const mpl_config* cfg, int batch, int use_packed, int cus, int* spw_out) {
+    if (!cfg || !spw_out || batch <= 0 || cus < 1 || cfg->num_views < 1 || cfg->num_views > MPL_MAX_VIEWS) return MPL_E_INVALID;
+    const bool any = spt_shape_general(cfg);
+    if (any && mpl_config_supported(cfg) != MPL_OK) return MPL_E_UNSUPPORTED;
+    const int cap = any ? spt_any_seq_cap(cfg->num_joints, cfg->dim) : SEQ;
+    int spw = cap;
+    for (int c = 1; c < cap; ++c)
+        if ((long long)cfg->num_views * ((batch + c - 1) / c) <= cus) { spw = c; break; }
+    *spw_out = spw;
+    if (any) return MPL_SPT_ANY;
+    if (!use_packed) return spw <= SPT_SMALL_SPW ? MPL_SPT_STAGED : MPL_SPT_FRAGS;
+    int ss = 1;
+    while (ss < spw) ss *= 2;
+    *spw_out = ss;
+    return MPL_SPT_PACKED;
+}
+
 int launch_spt(const mpl_config* cfg, const mpl_weights* w, const mpl_inputs* in, float* xs, int use_packed, hipStream_t s) {
-    // every other shape, and 17 / 32 / 8 on request, runs on the shape-general kernel (spt_any.hip)
-    if (cfg->num_joints != SJ || cfg->dim != SD || cfg->heads != SH || (cfg->flags & MPL_F_GENERIC_SPT))
-        return launch_spt_any(cfg, w, in, xs, s);
+    if (spt_shape_general(cfg)) return launch_spt_any(cfg, w, in, xs, s);
     if (cfg->num_views < 1 || cfg->num_views > MPL_MAX_VIEWS || in->batch <= 0) return MPL_E_INVALID;
     if (cfg->in_chans != 2 && cfg->in_chans != 3) return MPL_E_INVALID;
     const unsigned f = cfg->flags;
@@ -1397,27 +1437,14 @@ int launch_spt(const mpl_config* cfg, const mpl_weights* w, const mpl_inputs* in
     // >64 KiB of dynamic LDS needs an explicit opt-in, once per device
     if (int rc = kernel_lds_once<spt_kernel<false>>(SPT_LDS_BYTES)) return rc;
     if (int rc = kernel_lds_once<spt_kernel<true>>(SPT_SMALL_LDS_BYTES)) return rc;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return MPL_E_LAUNCH;
-    // Sequences per workgroup of the fp32-MFMA kernel: as few as keep the launch inside one wave of workgroups (one per CU), so
-    // that a single frame or a few hundred sequences use the whole chip with 2-3 live row tiles per workgroup instead of a few
-    // workgroups with 17; up to SPT_SMALL_SPW per workgroup run the staged form (spt_kernel<true>).
-    static std::atomic<int> n_cus[64];
-    int cus = n_cus[dev].load(std::memory_order_acquire);
-    if (cus == 0) {
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) return MPL_E_LAUNCH;
-        n_cus[dev].store(cus, std::memory_order_release);
-    }
-    int spw = SEQ;
-    for (int c = 1; c < SEQ; ++c)
-        if ((long long)cfg->num_views * ((in->batch + c - 1) / c) <= cus) { spw = c; break; }
-    // the packed-operand kernel takes 16, 8, 4, 2 or 1 sequences per workgroup (bitwise the same rows)
-    int ss = 1;
-    while (ss < spw) ss *= 2;
-    p.spw = use_packed ? ss : spw;
+    int cus = 0;
+    if (int rc = spt_device_cus(&cus)) return rc;
+    const int form = spt_form(cfg, in->batch, use_packed, cus, &p.spw);
+    if (form < 0) return form;
+    const int ss = p.spw;
     const int grid = cfg->num_views * ((in->batch + p.spw - 1) / p.spw);
     ProfScope prof(MPL_K_SPT, s);
-    if (use_packed) {
+    if (form == MPL_SPT_PACKED) {
         void (*k3)(const SptParams) = ss == 1 ? spt3_kernel<1> : ss == 2 ? spt3_kernel<2> : ss == 4 ? spt3_kernel<4> : ss == 8 ? spt3_kernel<8> : spt3_kernel<16>;
         const int rc = ss == 1 ? kernel_lds_once<spt3_kernel<1>>(SPT3_LDS_BYTES) : ss == 2 ? kernel_lds_once<spt3_kernel<2>>(SPT3_LDS_BYTES)
                      : ss == 4 ? kernel_lds_once<spt3_kernel<4>>(SPT3_LDS_BYTES) : ss == 8 ? kernel_lds_once<spt3_kernel<8>>(SPT3_LDS_BYTES)
@@ -1425,7 +1452,7 @@ int launch_spt(const mpl_config* cfg, const mpl_weights* w, const mpl_inputs* in
         if (rc) return rc;
         hipLaunchKernelGGL(k3, dim3(grid), dim3(NTHR), SPT3_LDS_BYTES, s, p);
     } else {
-        if (p.spw <= SPT_SMALL_SPW) hipLaunchKernelGGL(spt_kernel<true>, dim3(grid), dim3(NTHR), SPT_SMALL_LDS_BYTES, s, p);
+        if (form == MPL_SPT_STAGED) hipLaunchKernelGGL(spt_kernel<true>, dim3(grid), dim3(NTHR), SPT_SMALL_LDS_BYTES, s, p);
         else hipLaunchKernelGGL(spt_kernel<false>, dim3(grid), dim3(NTHR), SPT_LDS_BYTES, s, p);
     }
     return hip_check_launch();

@@ -272,6 +272,14 @@ __global__ __launch_bounds__(SA_THR) void spt_any_kernel(const SptAnyParams p) {
 
 }  // namespace
 
+// LDS bytes of one token row (X, A and T with their odd strides) and the most sequences a workgroup holds within 64 KiB (two
+// or more workgroups per CU), at least one
+size_t spt_any_row_bytes(int d) { return (size_t)(2 * odd_stride(d) + odd_stride(3 * d)) * sizeof(float); }
+int spt_any_seq_cap(int J, int d) {
+    const int s_lds = (int)((64 * 1024 - SA_W_FLOATS * sizeof(float)) / (spt_any_row_bytes(d) * J));
+    return s_lds < 1 ? 1 : s_lds;
+}
+
 int launch_spt_any(const mpl_config* cfg, const mpl_weights* w, const mpl_inputs* in, float* xs, hipStream_t s) {
     if (mpl_config_supported(cfg) != MPL_OK) return MPL_E_UNSUPPORTED;
     if (!w || !in || !xs || in->batch <= 0 || !w->spt_sets || !w->spatial_norm_w || !w->spatial_norm_b) return MPL_E_INVALID;
@@ -314,20 +322,16 @@ int launch_spt_any(const mpl_config* cfg, const mpl_weights* w, const mpl_inputs
         }
     }
     p.n_apps = n;
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        cus < 1)
-        return MPL_E_LAUNCH;
-    // Sequences per workgroup: as few as keep the launch inside one wave of workgroups (small batches use the whole chip), and at
-    // most as many as keep a workgroup's LDS within 64 KiB (two or more workgroups per CU); a sequence that alone needs more gets
-    // a workgroup of its own (J d <= 4096: < 84 KiB).
-    const size_t row_bytes = (size_t)(2 * p.xs_ld + p.ts_ld) * sizeof(float), w_bytes = SA_W_FLOATS * sizeof(float);
-    int s_lds = (int)((64 * 1024 - w_bytes) / (row_bytes * J));
-    if (s_lds < 1) s_lds = 1;
-    int spw = s_lds;
-    for (int c = 1; c < s_lds; ++c)
-        if ((long long)V * ((B + c - 1) / c) <= cus) { spw = c; break; }
+    int cus = 0;
+    if (int rc = spt_device_cus(&cus)) return rc;
+    // Sequences per workgroup: spt_form (spt.hip), the one rule mpl_spt_form reports by; a sequence that alone needs more than
+    // 64 KiB gets a workgroup of its own (J d <= 4096: < 84 KiB).
+    int spw = 0;
+    const int form = spt_form(cfg, B, 0, cus, &spw);
+    if (form < 0) return form;
+    if (form != MPL_SPT_ANY) return MPL_E_INVALID;       // a configuration launch_spt keeps for the tuned kernels
     p.spw = spw;
+    const size_t row_bytes = spt_any_row_bytes(d), w_bytes = SA_W_FLOATS * sizeof(float);
     const size_t lds = (size_t)spw * J * row_bytes + w_bytes;
     if (int rc = kernel_lds_once<spt_any_kernel>(160 * 1024)) return rc;
     if (lds > 160 * 1024) return MPL_E_UNSUPPORTED;

@@ -85,6 +85,22 @@ int main() {
     (void)mpl_block_stack_form_ex(1, 2, 544, 8, 13, 12, 0, 2, 0);
     EXPECT(mpl_block_stack_last_form() < 0);                                  // nothing was launched by this thread
 
+    // ---- the SPT launch rule query: with the compute units given it needs no device
+    {
+        int spw = -1;
+        mpl_config c17{17, 32, 2, 8, 3, 2, MPL_F_POS3D_LEARN, 0};
+        EXPECT(mpl_spt_form(nullptr, 8, 1, 256, &spw) < 0 && spw == -1);
+        EXPECT(mpl_spt_form(&c17, 0, 1, 256, &spw) < 0);
+        EXPECT(mpl_spt_form(&c17, 900, 0, 256, &spw) == MPL_SPT_FRAGS && spw == 11);
+        EXPECT(mpl_spt_form(&c17, 900, 1, 256, &spw) == MPL_SPT_PACKED && spw == 16);
+        EXPECT(mpl_spt_form(&c17, 85, 0, 256, nullptr) == MPL_SPT_STAGED);
+        c17.flags |= MPL_F_GENERIC_SPT;
+        EXPECT(mpl_spt_form(&c17, 1 << 30, 1, 256, &spw) == MPL_SPT_ANY && spw >= 1);
+        mpl_config c65{65, 32, 2, 8, 3, 2, MPL_F_POS3D_LEARN, 0};
+        EXPECT(mpl_spt_form(&c65, 8, 0, 256, &spw) < 0);
+        EXPECT(mpl_spt_form(&c17, 8, 0, 0, &spw) < 0);                           // asks the device: none here
+    }
+
     // ---- switches and per-device state
     EXPECT(mpl_x3_spin_limit(0) < 0);
     EXPECT(mpl_x3_spin_limit(31) < 0);

@@ -137,6 +137,8 @@ def test_shared_library_exports_every_symbol_declared_in_header():
     # the MPL_FORM_* codes of mpl_block_stack_form and the flag bits: the binding's constants are the header's
     forms = dict((n, int(v)) for n, v in re.findall(r"\bMPL_FORM_([A-Z0-9_]+)\s*=\s*(\d+)", header))
     assert forms and all(getattr(cabi, "FORM_" + n) == v for n, v in forms.items()) and set(cabi.FORM_KERNELS) == set(forms.values())
+    spt = dict((n, int(v)) for n, v in re.findall(r"\bMPL_SPT_([A-Z0-9_]+)\s*=\s*(\d+)", header))
+    assert spt and all(getattr(cabi, "SPT_" + n) == v for n, v in spt.items()) and set(cabi.SPT_KERNELS) == set(spt.values())
     assert int(re.search(r"#define\s+MPL_F_NO_SMALL_STACK\s+\(1u\s*<<\s*(\d+)\)", header).group(1)) == cabi.F_NO_SMALL_STACK.bit_length() - 1
     lib.mpl_block_stack_form.restype = ctypes.c_int
     assert lib.mpl_block_stack_form(0, 2, 544, 8, 13, 2, 0) < 0                   # invalid arguments are refused before any device query
