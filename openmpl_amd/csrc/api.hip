@@ -103,6 +103,19 @@ std::atomic<int> g_stack_mode{(getenv("MPL_X3_LAUNCHES") != nullptr ? 1 : 0) | (
 }  // namespace
 int mpl::stack_mode() { return g_stack_mode.load(); }
 
+// compute units of the current device (asked once per device)
+int mpl::device_cu_count(int* cus) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return MPL_E_LAUNCH;
+    static std::atomic<int> n_cus[64];
+    *cus = n_cus[dev].load(std::memory_order_acquire);
+    if (*cus == 0) {
+        if (hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || *cus < 1) return MPL_E_LAUNCH;
+        n_cus[dev].store(*cus, std::memory_order_release);
+    }
+    return MPL_OK;
+}
+
 namespace {
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -299,13 +312,6 @@ int block_stack_packed(float* x, int n_seq, int n_tok, int D, int H, const mpl_b
 
 thread_local int t_last_form = MPL_E_INVALID;  // MPL_FORM_* of this thread's most recent block-stack launch (mpl_block_stack_last_form)
 
-inline int device_cu_count(int* cus) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || *cus < 1)
-        return MPL_E_LAUNCH;
-    return MPL_OK;
-}
-
 // THE rule for "the small-batch engine (sm_stack.hip) takes this stack": block_stack_impl launches by it, mpl_block_stack_form
 // reports by it.  np = packed operand parts of the blocks (0 none, 2 fp16x2, 1 bf16: an explicit bf16 request keeps its engine);
 // raw = every nn.Linear / LayerNorm tensor of every scheduled block is present (the engine reads them in place); cus = compute
@@ -382,7 +388,7 @@ int block_stack_impl(float* x, int n_seq, int n_tok, int D, int H, const mpl_blo
     // slice whole heads (V in {1,2,4,8,16,32,64}; hd in {68,136}); otherwise as two kernels through `qkv`
     const bool fusable = qkv_attention_fusable(n_tok, D, H);
     // D = 32 blocks (keypoint-token FPT) that carry the operand of mpl_d32_pack in qkv_w3: everything but the attention is
-    // row-local and runs as two launches from split fp16 operands (spt.hip: d32_qkv_kernel, d32_mlp_kernel)
+    // row-local and runs as two launches from split fp16 operands (d32_blocks.hip: d32_qkv_kernel, d32_mlp_kernel)
     bool d32 = D == 32;
     for (int a = 0; a < n_apps && d32; ++a) {
         const mpl_block_weights& b = blocks[schedule[a]];
@@ -714,7 +720,7 @@ int mpl_spt_form(const mpl_config* cfg, int batch, int use_packed, int n_cus, in
     if (rc) return rc;
     if ((rc = mpl_config_supported(cfg))) return rc;
     if (batch <= 0) return MPL_E_INVALID;
-    if (n_cus <= 0 && (rc = spt_device_cus(&n_cus))) return rc;
+    if (n_cus <= 0 && (rc = device_cu_count(&n_cus))) return rc;
     int spw = 0;
     rc = spt_form(cfg, batch, use_packed, n_cus, &spw);
     if (rc >= 0 && seq_per_wg) *seq_per_wg = spw;

@@ -24,7 +24,7 @@ inline const char* lab_getenv(const char* name) {
 }
 
 // x = hi + lo in fp16: hi = fp16(x), lo = fp16(x - hi) (RNE; the residual is exact in fp32; subnormal results are kept) -- the
-// operand split of the fp16x2 engines (h2_phase.hpp, spt.hip).  8 values per lane = one MFMA fragment per part.
+// operand split of the fp16x2 engines (h2_phase.hpp, spt_pack.hpp).  8 values per lane = one MFMA fragment per part.
 // Round 6: the lo part is ONE v_fma_mix{lo,hi}_f16 per value (fp16(hi * -1.0 + x): hi read as fp16, the fma in fp32, one rounding
 // to fp16) instead of v_cvt_f32_f16 + v_sub_f32 + half a v_cvt_pk_f16_f32: 20 VALU per split of 8 values instead of 32-36 --
 // the LayerNorm GEMMs of the FPT stack split one A fragment per k-tile and wave, the SPT kernel is VALU-bound.  Bit for bit the
@@ -140,6 +140,8 @@ struct ProfScope {
     int slot;
     hipStream_t stream;
 };
+
+int device_cu_count(int* cus);      // compute units of the current device, asked once per device (api.hip); MPL_E_LAUNCH when it cannot be had
 
 inline int hip_check_launch() {
     hipError_t e = hipGetLastError();
@@ -281,15 +283,14 @@ bool token_attention_wide_ok(int n_tok, int hd);
 int launch_token_attention_wide(const float* qkv, int n_seq, int n_tok, int dim, int heads, float* out, hipStream_t s);
 // the same (n_tok <= 32 only) with the output rounded to bf16 on the way out: out16 [n_seq * n_tok][ldo], columns >= dim untouched
 int launch_token_attention_bf16(const float* qkv, int n_seq, int n_tok, int dim, int heads, unsigned short* out16, int ldo, hipStream_t s);
-// use_packed: every SPT block carries the split operand of mpl_spt_pack in qkv_w3 (spt3_kernel: Linear layers on the bf16
-// matrix cores); else the fp32-MFMA kernel reads the nn.Linear weights in place
+// use_packed: every SPT block carries the split operand of mpl_spt_pack in qkv_w3 (spt_packed.hip, spt3_kernel: Linear layers on the
+// fp16 matrix cores); else the fp32-MFMA kernel (spt_native.hip) reads the nn.Linear weights in place
 int launch_spt(const mpl_config* cfg, const mpl_weights* w, const mpl_inputs* in, float* xs, int use_packed, hipStream_t s);
 // any J / d / H inside mpl_config_supported (spt_any.hip): fp32 FMA, the nn.Linear weights read in place
 int launch_spt_any(const mpl_config* cfg, const mpl_weights* w, const mpl_inputs* in, float* xs, hipStream_t s);
 // THE rule for the kernel (MPL_SPT_* of mpl_hip.h) and the sequences per workgroup (*spw; SS of spt3_kernel<SS> for MPL_SPT_PACKED)
 // an SPT launch for `batch` poses takes on a device of `cus` compute units (spt.hip): both launchers follow it, mpl_spt_form reports it
 int spt_form(const mpl_config* cfg, int batch, int use_packed, int cus, int* spw);
-int spt_device_cus(int* cus);
 size_t spt_any_row_bytes(int d);
 int spt_any_seq_cap(int J, int d);
 size_t spt_pack_bytes();

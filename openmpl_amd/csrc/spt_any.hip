@@ -323,7 +323,7 @@ int launch_spt_any(const mpl_config* cfg, const mpl_weights* w, const mpl_inputs
     }
     p.n_apps = n;
     int cus = 0;
-    if (int rc = spt_device_cus(&cus)) return rc;
+    if (int rc = device_cu_count(&cus)) return rc;
     // Sequences per workgroup: spt_form (spt.hip), the one rule mpl_spt_form reports by; a sequence that alone needs more than
     // 64 KiB gets a workgroup of its own (J d <= 4096: < 84 KiB).
     int spw = 0;

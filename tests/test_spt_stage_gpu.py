@@ -20,7 +20,8 @@ at TOL = 1e-4 under "fp32" and "fp32_mfma".
 
 e32 of these cases (CPU, at the largest batch), max-scaled / norm-wise: 2.5e-7 .. 5.5e-7 / 0.8e-7 .. 2.7e-7 at 17 / 32 / 8,
 2.2e-7 .. 3.7e-7 / 1.2e-7 .. 1.7e-7 at the other shapes.  The kernels' own worst errors per engine are printed by every case
-("worst so far"); they have not been recorded here yet -- the bound does not come from them.
+("worst so far"); measured on an MI355X over the whole file, max-scaled / norm-wise: packed 6.4e-7 / 3.3e-7, native 5.5e-7 /
+2.4e-7, generic 6.2e-7 / 2.7e-7 -- the bound does not come from them.
 """
 import ctypes as C
 

@@ -1,7 +1,8 @@
 #!/bin/bash
 # Prebuild library variants of ONE source file (default h2_gemm.hip) for A/B runs inside one gpurun call:
 #   bash tools/build_variants.sh [-f file.hip] tag1="-DH2_DBG=1" tag2="-DH2_ABL=2" ...   ->  build_tmp/lib_<tag>.so
-# (-DMPL_LAB is passed for the varied file: the H2_* switches are compile errors in the product build, csrc/h2_phase.hpp)
+# (-DMPL_LAB is passed for the varied file: the H2_* switches are compile errors in the product build, csrc/h2_phase.hpp; -f spt.hip lab=""
+# makes the SPT launcher read MPL_SPT_ABL, -f spt_native.hip x="..." / -f spt_packed.hip / -f d32_blocks.hip vary one kernel file of the stage)
 # The other objects are compiled once (build_tmp/obj).  On the GPU box: cp build_tmp/lib_<tag>.so openmpl_amd/lib/libmpl_hip.so
 # (the source hash stamp of the default build stays valid, so cabi.load() does not rebuild).
 set -e

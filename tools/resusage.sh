@@ -1,5 +1,6 @@
 #!/bin/bash
 # usage: tools/resusage.sh <file.hip> [extra hipcc flags]  -- per-kernel registers / spills / scratch of one translation unit
+# (the SPT stage: spt_native.hip, spt_packed.hip, d32_blocks.hip)
 f=$1; shift
 cd "$(dirname "$0")/../openmpl_amd/csrc"
 hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC "$@" -c "$f" -o /tmp/resusage_$$.o -Rpass-analysis=kernel-resource-usage 2>&1 | \

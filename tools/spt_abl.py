@@ -1,4 +1,6 @@
-"""(needs a laboratory build of spt.hip: bash tools/build_variants.sh -f spt.hip lab="" -> build_tmp/lib_lab.so; the product library ignores MPL_SPT_ABL)
+"""(needs a laboratory build of spt.hip, which reads MPL_SPT_ABL: bash tools/build_variants.sh -f spt.hip lab="" -> build_tmp/lib_lab.so; the product
+library ignores the variable.  The bits below are those of spt3_kernel, spt_packed.hip; spt_kernel heeds its own -- spt_stage.hpp SptParams::abl --
+only where spt_native.hip is a laboratory build too: MPL_HIPCC_FLAGS=-DMPL_LAB python -m openmpl_amd.build)
 Time of the fused SPT kernel with one phase compiled... switched off at a time (MPL_SPT_ABL bits: 8 qkv, 1 attention, 32 proj,
 64 fc1 + GELU, 128 fc2; results are garbage): [SPT_V=2 SPT_B=256] python tools/spt_abl.py"""
 import os, subprocess, sys
