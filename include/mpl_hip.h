@@ -375,6 +375,51 @@ int mpl_pose_metrics(const float *output, const float *target, const float *weig
 int mpl_pose_metrics_ex(const float *output, const float *target, const float *weight, int batch, int joints,
                         const float *scale3, const float *offset3, uint32_t not_consider_mask, float *result, void *stream);
 
+/* ---- device-resident evaluator of a whole validation run (csrc/evaluate.hip; the second half of rank f3): everything
+ * validate() does on the host after `model(...)`, accumulated on the device batch by batch and read back once.  Every entry
+ * point is stream-ordered and never synchronises; sums are fp64 and folded in a fixed order (bitwise reproducible runs).
+ * Replaces, per batch: function_mpl.py:387-399 (criterion, 4 x .item(), AverageMeter weighted by len(input) * batch),
+ * :474-494 (D2H copy, room de-normalisation, all_preds / all_gts / all_3d_confs); per run: :612-634 and evaluate() :670-785
+ * (OUTPUT_IN_METER factor, relative mode, `conf_3d <= 0` NaN mask, calc_mpjpe / calc_distance_per_dim of evaluate.py:91-125,
+ * the per-action breakdown); criteria loss.py:39-57 (MPJPE, LOSS.WEIGHT_AXIS :55-56), :59-104 (L1, MSE), :110-124
+ * (Weighted_MPJPE), :127-146 (MPJPE_KADKHODA).
+ * State: mpl_eval_state_bytes(n_sel, n_groups) bytes of device memory (0 = shape refused), 8-byte aligned, cleared by
+ * mpl_eval_reset.  n_sel = joints of the selection `u` (all_preds[:, u, :], <= 64, entry 0 is the root), n_groups = 1 +
+ * caller's classes (group 0 = all samples; <= MPL_EVAL_MAX_GROUPS).
+ * mpl_eval_accumulate: one batch.  output/target (B,J,3); x1/x2 (B,J,3) the two intermediate poses of the kadkhod head
+ * (MPJPE_KADKHODA only); weight (B,J) (Weighted_MPJPE, MPJPE with weight_axis); conf_3d (B,J) optional, indexed through the
+ * selection like the poses; group (B) int32 optional when n_groups == 1: a sample counts in group 0 and, when 1 <= id <
+ * n_groups, in its own.  keep_pred/keep_tgt (both or neither): (keep_capacity,J,3) device buffers that receive the batch's
+ * de-normalised poses at the run's sample offset (rows beyond the capacity are dropped).  MPJPE with weight_axis follows the
+ * broadcast of loss.py:56 ((B,J,1) * (B,J): defined for B == 1, J == 1 or B == J only, MPL_E_INVALID otherwise; B <= 64).
+ * While the device's error word is set the batch adds nothing and the state is marked poisoned: every report is NaN.
+ * mpl_eval_report: report (device, mpl_eval_report_size doubles): [0] loss, [1..3] loss per axis (AverageMeter.avg),
+ * [4] samples fed, [5] poisoned, [6..7] 0; then for pass p (0 absolute, 1 relative) and group g, at 8 + (p * n_groups + g) *
+ * (4 * n_sel + 5): pjpe[n_sel], mpjpe, dist[n_sel][3], dist_mean[3], samples of the group (0: the fields are NaN).  Bit k of
+ * not_consider_mask deletes SELECTED joint k from mpjpe (np.delete semantics, evaluate.py:101-104); all 64 joints can be named.
+ * MPL_E_INVALID: bad arguments; MPL_E_UNSUPPORTED: more than 64 joints or MPL_EVAL_MAX_GROUPS groups -- before any launch. */
+#define MPL_EVAL_MAX_GROUPS 32
+enum { MPL_CRIT_MPJPE = 0, MPL_CRIT_WEIGHTED_MPJPE = 1, MPL_CRIT_L1 = 2, MPL_CRIT_MSE = 3, MPL_CRIT_MPJPE_KADKHODA = 4 };
+typedef struct mpl_eval_options {
+    int32_t criterion;       /* MPL_CRIT_* */
+    int32_t has_weight_axis; /* LOSS.WEIGHT_AXIS is not None (MPJPE, L1, MSE) */
+    float weight_axis[3];
+    float scale[3];          /* room de-normalisation x * scale + offset (identity: 1, 0) */
+    float offset[3];
+    float metre_factor;      /* 100 when DATASET.OUTPUT_IN_METER, else 1 */
+    int32_t n_views;         /* len(input): the AverageMeter weight of a batch is n_views * B */
+    int32_t n_sel;
+    int32_t n_groups;
+    uint8_t sel[64];         /* the selection `u`: source joint of selected joint k */
+} mpl_eval_options;
+size_t mpl_eval_state_bytes(int n_sel, int n_groups);
+int mpl_eval_reset(void *state, int n_sel, int n_groups, void *stream);
+int mpl_eval_accumulate(void *state, const mpl_eval_options *opt, const float *output, const float *x1, const float *x2,
+                        const float *target, const float *weight, const float *conf_3d, const int32_t *group, int batch,
+                        int joints, float *keep_pred, float *keep_tgt, long long keep_capacity, void *stream);
+int mpl_eval_report_size(int n_sel, int n_groups);
+int mpl_eval_report(const void *state, int n_sel, int n_groups, uint64_t not_consider_mask, double *report, void *stream);
+
 /* ---- fp16x2 split-operand engine (csrc/h2_gemm.hip): "fp32" precision of MultiView_MPL (the default).
  * mpl_pack_h2: derived operand of one nn.Linear (W (N,K) row-major, bias (N)), optionally with the LayerNorm in front of it
  * folded in (ln_w, ln_b of length K, or both NULL).  dst: mpl_pack_h2_bytes(N, K) bytes (0 = the shape has no layout:

@@ -8,3 +8,11 @@ def check_device(device: int = -1, synchronize: bool = True):
     batch is covered by the next call into the library, the last one only by this."""
     from . import cabi
     cabi.raise_if_device_error(device, synchronize)
+
+
+def __getattr__(name):
+    # PoseEvaluator lives in a module that imports torch and loads the native library: resolved on first use
+    if name == "PoseEvaluator":
+        from .evaluate import PoseEvaluator
+        return PoseEvaluator
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

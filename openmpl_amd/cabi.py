@@ -79,6 +79,17 @@ class Weights(C.Structure):
                 ("head_w", _fp), ("head_b", _fp), ("spt_packed", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+# mpl_eval_accumulate(): criteria (MPL_CRIT_* of mpl_hip.h) and the cap on groups
+CRIT_MPJPE, CRIT_WEIGHTED_MPJPE, CRIT_L1, CRIT_MSE, CRIT_MPJPE_KADKHODA = range(5)
+EVAL_MAX_GROUPS = 32
+
+
+class EvalOptions(C.Structure):
+    _fields_ = [("criterion", C.c_int32), ("has_weight_axis", C.c_int32), ("weight_axis", C.c_float * 3), ("scale", C.c_float * 3),
+                ("offset", C.c_float * 3), ("metre_factor", C.c_float), ("n_views", C.c_int32), ("n_sel", C.c_int32),
+                ("n_groups", C.c_int32), ("sel", C.c_uint8 * 64)]
+
+
 class Inputs(C.Structure):
     _fields_ = [("batch", C.c_int32), ("reserved", C.c_int32),
                 ("poses", _fp * MPL_MAX_VIEWS), ("rays", _fp * MPL_MAX_VIEWS), ("centers", _fp * MPL_MAX_VIEWS)]
@@ -87,7 +98,7 @@ class Inputs(C.Structure):
 EXPORTS = ("mpl_hip_abi_version", "mpl_hip_error_string", "mpl_config_supported", "mpl_fpt_width", "mpl_forward_workspace_bytes",
            "mpl_forward", "mpl_spt_tokens", "mpl_block_stack_workspace_bytes", "mpl_block_stack", "mpl_block_stack_ex",
            "mpl_ln_linear", "mpl_spt_pack_bytes", "mpl_spt_pack", "mpl_d32_pack", "mpl_pack_bf16_bytes", "mpl_pack_bf16", "mpl_bf16_operand_layout", "mpl_pack_bf16_any_bytes", "mpl_pack_bf16_any", "mpl_ln_linear_bf16_any_workspace_bytes", "mpl_ln_linear_bf16_any", "mpl_pack_h2_bytes", "mpl_pack_h2", "mpl_pack_h2_scaled", "mpl_pack_h2_out_scale", "mpl_ln_linear_h2_workspace_bytes", "mpl_ln_linear_h2", "mpl_x3_debug_buffer", "mpl_x3_stack_mode", "mpl_block_stack_form", "mpl_block_stack_form_ex", "mpl_block_stack_last_form", "mpl_spt_form", "mpl_device_error", "mpl_device_error_clear", "mpl_x3_spin_limit", "mpl_token_attention", "mpl_fuse_head", "mpl_view_fuse", "mpl_view_norm",
-           "mpl_layernorm", "mpl_linear", "mpl_pose_metrics_size", "mpl_pose_metrics", "mpl_pose_metrics_ex", "mpl_prepare_inputs", "mpl_profile_start",
+           "mpl_layernorm", "mpl_linear", "mpl_pose_metrics_size", "mpl_pose_metrics", "mpl_pose_metrics_ex", "mpl_eval_state_bytes", "mpl_eval_reset", "mpl_eval_accumulate", "mpl_eval_report_size", "mpl_eval_report", "mpl_prepare_inputs", "mpl_profile_start",
            "mpl_profile_stop")
 KINDS = ("spt", "row_stats", "gemm", "attention", "fuse_head", "pack")
 
@@ -223,6 +234,17 @@ def load():
         lib.mpl_pose_metrics.argtypes = [_fp, _fp, _fp, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), _fp, _fp]
         lib.mpl_pose_metrics_ex.restype = C.c_int
         lib.mpl_pose_metrics_ex.argtypes = [_fp, _fp, _fp, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, _fp, _fp]
+        lib.mpl_eval_state_bytes.restype = C.c_size_t
+        lib.mpl_eval_state_bytes.argtypes = [C.c_int, C.c_int]
+        lib.mpl_eval_reset.restype = C.c_int
+        lib.mpl_eval_reset.argtypes = [_fp, C.c_int, C.c_int, _fp]
+        lib.mpl_eval_accumulate.restype = C.c_int
+        lib.mpl_eval_accumulate.argtypes = [_fp, C.POINTER(EvalOptions), _fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_int, C.c_int, _fp, _fp,
+                                            C.c_longlong, _fp]
+        lib.mpl_eval_report_size.restype = C.c_int
+        lib.mpl_eval_report_size.argtypes = [C.c_int, C.c_int]
+        lib.mpl_eval_report.restype = C.c_int
+        lib.mpl_eval_report.argtypes = [_fp, C.c_int, C.c_int, C.c_uint64, _fp, _fp]
         lib.mpl_prepare_inputs.restype = C.c_int
         lib.mpl_prepare_inputs.argtypes = [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int,
                                            C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_fp), _fp]

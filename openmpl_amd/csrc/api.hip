@@ -830,6 +830,29 @@ int mpl_pose_metrics_ex(const float* output, const float* target, const float* w
     return launch_pose_metrics(output, target, weight, batch, joints, scale3, offset3, not_consider_mask, result, (hipStream_t)stream);
 }
 
+size_t mpl_eval_state_bytes(int n_sel, int n_groups) { return eval_state_bytes(n_sel, n_groups); }
+
+int mpl_eval_reset(void* state, int n_sel, int n_groups, void* stream) {
+    clear_stale_hip_error();
+    return launch_eval_reset(state, n_sel, n_groups, (hipStream_t)stream);
+}
+
+int mpl_eval_accumulate(void* state, const mpl_eval_options* opt, const float* output, const float* x1, const float* x2,
+                        const float* target, const float* weight, const float* conf_3d, const int32_t* group, int batch, int joints,
+                        float* keep_pred, float* keep_tgt, long long keep_capacity, void* stream) {
+    clear_stale_hip_error();
+    if (int rc = earlier_device_failure()) return rc;
+    return launch_eval_accumulate(state, opt, output, x1, x2, target, weight, conf_3d, group, batch, joints, keep_pred, keep_tgt,
+                                  keep_capacity, (hipStream_t)stream);
+}
+
+int mpl_eval_report_size(int n_sel, int n_groups) { return eval_report_doubles(n_sel, n_groups); }
+
+int mpl_eval_report(const void* state, int n_sel, int n_groups, uint64_t not_consider_mask, double* report, void* stream) {
+    clear_stale_hip_error();
+    return launch_eval_report(state, n_sel, n_groups, not_consider_mask, report, (hipStream_t)stream);
+}
+
 int mpl_forward(const mpl_config* cfg, const mpl_weights* w, const mpl_inputs* in, float* out, void* workspace,
                 size_t workspace_bytes, void* stream) {
     clear_stale_hip_error();

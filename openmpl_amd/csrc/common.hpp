@@ -311,6 +311,15 @@ int launch_linear_act(const float* xa, int Ka, int lda, const float* xb, int Kb,
 int launch_pose_metrics(const float* out, const float* tgt, const float* wgt, int B, int J, const float* scale3,
                         const float* offset3, unsigned skip_mask, float* res, hipStream_t s);
 
+// evaluate.hip: the run-level evaluator (mpl_eval_*)
+size_t eval_state_bytes(int n_sel, int n_groups);
+int launch_eval_reset(void* state, int n_sel, int n_groups, hipStream_t s);
+int launch_eval_accumulate(void* state, const mpl_eval_options* o, const float* out, const float* x1, const float* x2,
+                           const float* tgt, const float* wgt, const float* conf, const int32_t* gid, int B, int J, float* keep_pred,
+                           float* keep_tgt, long long keep_cap, hipStream_t s);
+int eval_report_doubles(int n_sel, int n_groups);
+int launch_eval_report(const void* state, int n_sel, int n_groups, uint64_t skip_mask, double* rep, hipStream_t s);
+
 int launch_prepare_inputs(const float* px, const float* conf, const double* cams_dev, int B, int V, int J, float w, float h,
                           int norm_in, int norm_cam, float* const* poses, float* const* rays, float* const* centers,
                           hipStream_t s);
