@@ -25,6 +25,8 @@
  *   mpl_ln_linear          nn.LayerNorm + nn.Linear (+GELU | +residual) pairs inside Block
  *   mpl_token_attention    Attention.forward minus the two Linear layers   :55-64
  *   mpl_fuse_head          forward_features tail :425-446 + default head :283-286,:521-523
+ *   mpl_triangulate_rays   lib/multiviews/triangulate.py (the triangulation baseline)
+ *   mpl_epipolar_errors    lib/utils/calib.py:94-169 (distance_between_two_skew_lines, smart_pseudo_remove_weight)
  */
 #ifndef MPL_HIP_H_
 #define MPL_HIP_H_
@@ -358,6 +360,33 @@ int mpl_linear(const float *xa, int Ka, const float *xb, int Kb, int M, const fl
 int mpl_prepare_inputs(const float *joints_px, const float *conf, const double *cams_dev, int batch, int views,
                        int joints, float img_w, float img_h, int normalize_inputs, int normalize_cameras,
                        float *const *poses, float *const *rays, float *const *centers, void *stream);
+
+/* ---- multi-view geometry on the tensors of mpl_inputs, csrc/geometry.hip: rays[v] (B,J,3) is a world point on the line of
+ * sight of view v (joints_dataset_mpl.py:872-904), centers[v] (B,1,3) the camera centre; line v goes through c_v along
+ * d_v = (r_v - c_v) / |r_v - c_v|.  rays / centers / conf are HOST arrays of `views` device pointers; conf may be NULL (every
+ * confidence 1).  conf_stride: 1 = conf[v] is a (B,J) tensor; 3 = conf[v] is one of the model's own (B,J,3) pose tensors
+ * (mpl_inputs.poses), whose channel 2 is read in place.  fp64 arithmetic on the fp32 inputs, fp32 outputs, one work item per
+ * (sample, joint), no floating-point atomics: identical bits from run to run, and a sample does not depend on its batch mates.
+ * MPL_E_INVALID: a NULL pointer, a non-positive size, a conf_stride other than 1 or 3; MPL_E_UNSUPPORTED: views > MPL_MAX_VIEWS,
+ * joints > 64, batch * joints > 2^30, views < 2 for mpl_epipolar_errors -- before any launch.  Neither call looks at or sets
+ * the device error word.
+ * mpl_triangulate_rays: the geometric baseline of a multi-view lifter, in place of lib/multiviews/triangulate.py (pymvg, on the
+ * host).  out_points (B,J,3) = cbar + A^-1 b with A = sum_v w_v (I - d_v d_v^T), b = sum_v w_v (I - d_v d_v^T)(c_v - cbar), cbar
+ * the mean camera centre of the sample, w_v the confidence of (sample, view, joint); a view with w_v <= 0 or a non-finite w_v does
+ * not take part.  out_residual (B,J) = sqrt(sum_v w_v dist(x, line_v)^2 / sum_v w_v).  A joint with fewer than two views taking
+ * part, or with det(A / sum w) < 1e-10 (two views: sin^2(angle) / 4, i.e. lines within about 2e-5 rad of parallel), is
+ * degenerate: its point and its residual are NaN.
+ * mpl_epipolar_errors: lib/utils/calib.py:116-169 smart_pseudo_remove_weight with :94-113 distance_between_two_skew_lines, which
+ * the multi-view datasets run in numpy per sample.  out_err (B,V,J): err[b,i,j] = conf_i / (V - 1) * sum_{k != i} dist(line_i,
+ * line_k), dist = |(c_k - c_i) . (d_i x d_k)| / |d_i x d_k| (:162-165: every pair counts, the confidence scales only the view's
+ * own total).  The one deviation: where |d_i x d_k|^2 < 1e-20 the reference divides 0 by 0; here the pair contributes the
+ * distance of c_k to line i, the limit of the formula.  weight_in / weight_out (both or neither), (B,V,J): weight_out = 0 where
+ * err > threshold, weight_in elsewhere (:167-168); two distinct buffers. */
+int mpl_triangulate_rays(const float *const *rays, const float *const *centers, const float *const *conf, int conf_stride,
+                         int batch, int views, int joints, float *out_points, float *out_residual, void *stream);
+int mpl_epipolar_errors(const float *const *rays, const float *const *centers, const float *const *conf, int conf_stride,
+                        int batch, int views, int joints, float *out_err, const float *weight_in, float threshold,
+                        float *weight_out, void *stream);
 
 /* ---- output-side epilogue (the step right after the path): what validate() does on the host
  * with `output.clone().cpu().numpy()` -- room de-normalisation x*scale+offset (function_mpl.py:476-488, host float[3]

@@ -15,4 +15,7 @@ def __getattr__(name):
     if name == "PoseEvaluator":
         from .evaluate import PoseEvaluator
         return PoseEvaluator
+    if name in ("triangulate_rays", "epipolar_errors", "consistency_weights"):
+        from . import geometry
+        return getattr(geometry, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -814,6 +814,20 @@ int mpl_prepare_inputs(const float* joints_px, const float* conf, const double* 
                                  normalize_cameras, poses, rays, centers, (hipStream_t)stream);
 }
 
+int mpl_triangulate_rays(const float* const* rays, const float* const* centers, const float* const* conf, int conf_stride, int batch,
+                         int views, int joints, float* out_points, float* out_residual, void* stream) {
+    clear_stale_hip_error();
+    return launch_triangulate_rays(rays, centers, conf, conf_stride, batch, views, joints, out_points, out_residual, (hipStream_t)stream);
+}
+
+int mpl_epipolar_errors(const float* const* rays, const float* const* centers, const float* const* conf, int conf_stride, int batch,
+                        int views, int joints, float* out_err, const float* weight_in, float threshold, float* weight_out,
+                        void* stream) {
+    clear_stale_hip_error();
+    return launch_epipolar_errors(rays, centers, conf, conf_stride, batch, views, joints, out_err, weight_in, threshold, weight_out,
+                                  (hipStream_t)stream);
+}
+
 int mpl_pose_metrics_size(int joints) { return 4 + 2 * (joints + 1) + 3 * joints + 3; }
 
 int mpl_pose_metrics(const float* output, const float* target, const float* weight, int batch, int joints,

@@ -324,4 +324,10 @@ int launch_prepare_inputs(const float* px, const float* conf, const double* cams
                           int norm_in, int norm_cam, float* const* poses, float* const* rays, float* const* centers,
                           hipStream_t s);
 
+// geometry.hip: triangulation of the model's rays and the epipolar consistency score (mpl_triangulate_rays, mpl_epipolar_errors)
+int launch_triangulate_rays(const float* const* rays, const float* const* centers, const float* const* conf, int conf_stride, int B,
+                            int V, int J, float* points, float* residual, hipStream_t s);
+int launch_epipolar_errors(const float* const* rays, const float* const* centers, const float* const* conf, int conf_stride, int B,
+                           int V, int J, float* err, const float* weight_in, float threshold, float* weight_out, hipStream_t s);
+
 }  // namespace mpl

@@ -1,0 +1,122 @@
+"""Multi-view geometry on the tensors the model call receives: triangulation of the rays and epipolar consistency of the detections.
+
+Reference: lib/multiviews/triangulate.py (the triangulation baseline, on pymvg), lib/utils/calib.py:94-113
+distance_between_two_skew_lines and :116-169 smart_pseudo_remove_weight (numpy, per sample, inside the datasets' __getitem__).
+`rays` is a list of V (B,J,3) tensors, a world point on each joint's line of sight (joints_dataset_mpl.py:872-904), `centers` a list
+of V (B,1,3) camera centres -- what prepare_inputs returns and `model(input, centers=centers, rays=rays)` takes.  `conf` is a list of
+V tensors, each (B,J) or one of the model's own (B,J,3) pose tensors, whose channel 2 is read in place.  Two HIP kernels through the
+C ABI (mpl_triangulate_rays, mpl_epipolar_errors, csrc/geometry.hip) on the current stream; no synchronisation, no CPU path.
+"""
+from __future__ import annotations
+
+from typing import List, Optional, Sequence, Tuple
+
+import torch
+
+from . import cabi
+
+
+def _listed(lst, what, n=None):
+    if not isinstance(lst, (list, tuple)) or len(lst) == 0 or not all(isinstance(t, torch.Tensor) for t in lst):
+        raise RuntimeError("%s must be a non-empty list of tensors, one per view" % what)
+    if n is not None and len(lst) != n:
+        raise RuntimeError("%s holds %d tensors for %d views" % (what, len(lst), n))
+    return list(lst)
+
+
+def _lines(rays, centers, conf, weight=None):
+    """Shapes first, then dtypes, then devices (so that each complaint names the argument it is about, with or without a GPU)
+    -> contiguous float32 GPU tensors, the confidence stride and the sizes."""
+    rays = _listed(rays, "rays")
+    V = len(rays)
+    if rays[0].ndim != 3 or rays[0].shape[2] != 3 or rays[0].shape[0] < 1 or rays[0].shape[1] < 1:
+        raise RuntimeError("rays[0]: expected shape (B,J,3), got %s" % (tuple(rays[0].shape),))
+    B, J, _ = rays[0].shape
+    groups = [("rays", rays, (B, J, 3)), ("centers", _listed(centers, "centers", V), (B, 1, 3))]
+    stride = 1
+    if conf is not None:
+        conf = _listed(conf, "conf", V)
+        stride = 3 if conf[0].ndim == 3 else 1           # one of the model's pose tensors: x, y, confidence
+        groups.append(("conf", conf, (B, J, 3) if stride == 3 else (B, J)))
+    if weight is not None:
+        groups.append(("weight", _listed(weight, "weight", V), (B, J)))
+    for what, lst, shape in groups:
+        for v, t in enumerate(lst):
+            if tuple(t.shape) != shape:
+                raise RuntimeError("%s[%d]: expected shape %s, got %s" % (what, v, shape, tuple(t.shape)))
+    for what, lst, _ in groups:
+        for v, t in enumerate(lst):
+            if t.dtype != torch.float32:
+                raise RuntimeError("float32 tensors required (%s[%d] is %s)" % (what, v, t.dtype))
+    dev = rays[0].device
+    for what, lst, _ in groups:
+        for v, t in enumerate(lst):
+            if t.device.type != "cuda":
+                raise RuntimeError("the geometry kernels have no CPU path: %s[%d] must live on a GPU" % (what, v))
+            if t.device != dev:
+                raise RuntimeError("%s[%d] is on %s, rays[0] on %s" % (what, v, t.device, dev))
+    if V > cabi.MPL_MAX_VIEWS or J > 64:
+        raise NotImplementedError("at most %d views and 64 joints (got %d, %d)" % (cabi.MPL_MAX_VIEWS, V, J))
+    out = [[t.contiguous() for t in lst] for _, lst, _ in groups]
+    rays, centers = out[0], out[1]
+    conf = out[2] if conf is not None else None
+    weight = out[-1] if weight is not None else None
+    return rays, centers, conf, weight, stride, B, V, J
+
+
+def _table(lst):
+    return None if lst is None else (cabi._fp * len(lst))(*[t.data_ptr() for t in lst])
+
+
+def triangulate_rays(rays: Sequence[torch.Tensor], centers: Sequence[torch.Tensor], conf: Optional[Sequence[torch.Tensor]] = None
+                     ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The point closest to the V lines, weighted by the confidences: (points (B,J,3), residual (B,J)), residual the weighted
+    root-mean-square distance of the point to its lines.  A view whose confidence is <= 0 or not finite does not take part; a
+    joint with fewer than two views taking part, or with lines within about 2e-5 rad of parallel, is NaN in both outputs.
+    `points` is what PoseEvaluator.update(points, target, ...) takes."""
+    rays, centers, conf, _, stride, B, V, J = _lines(rays, centers, conf)
+    dev = rays[0].device
+    lib = cabi.load()
+    points = torch.empty((B, J, 3), dtype=torch.float32, device=dev)
+    residual = torch.empty((B, J), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.mpl_triangulate_rays(_table(rays), _table(centers), _table(conf), stride, B, V, J, points.data_ptr(),
+                                      residual.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    cabi.check(rc, "mpl_triangulate_rays")
+    return points, residual
+
+
+def _epipolar(rays, centers, conf, weight, threshold):
+    rays, centers, conf, weight, stride, B, V, J = _lines(rays, centers, conf, weight)
+    if V < 2:
+        raise NotImplementedError("the epipolar error needs at least two views")
+    dev = rays[0].device
+    w_in = w_out = None
+    if weight is not None:
+        w_in = torch.stack(weight, dim=1)                # (B,V,J), the layout of the errors
+        w_out = torch.empty_like(w_in)
+    lib = cabi.load()
+    err = torch.empty((B, V, J), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.mpl_epipolar_errors(_table(rays), _table(centers), _table(conf), stride, B, V, J, err.data_ptr(),
+                                     None if w_in is None else w_in.data_ptr(), float(threshold),
+                                     None if w_out is None else w_out.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    cabi.check(rc, "mpl_epipolar_errors")
+    return err, w_out
+
+
+def epipolar_errors(rays: Sequence[torch.Tensor], centers: Sequence[torch.Tensor], conf: Optional[Sequence[torch.Tensor]] = None
+                    ) -> torch.Tensor:
+    """(B,V,J): err[b,i,j] = conf_i / (V - 1) * sum over the other views k of the distance between lines i and k of joint j
+    (calib.py:160-165; conf_i = 1 without confidences).  Parallel lines, where the reference divides 0 by 0, contribute the
+    distance of the other centre to line i."""
+    return _epipolar(rays, centers, conf, None, 0.0)[0]
+
+
+def consistency_weights(rays: Sequence[torch.Tensor], centers: Sequence[torch.Tensor], conf: Optional[Sequence[torch.Tensor]],
+                        weight: Sequence[torch.Tensor], threshold: float = 5.0) -> List[torch.Tensor]:
+    """smart_pseudo_remove_weight (calib.py:116-169) for a whole batch: `weight` is a list of V (B,J) tensors; returns their copies
+    with the joints whose epipolar error exceeds `threshold` set to 0 (views of one (B,V,J) tensor)."""
+    if weight is None:
+        raise RuntimeError("weight must be a non-empty list of tensors, one per view")
+    return list(_epipolar(rays, centers, conf, weight, threshold)[1].unbind(1))
