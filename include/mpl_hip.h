@@ -27,6 +27,7 @@
  *   mpl_fuse_head          forward_features tail :425-446 + default head :283-286,:521-523
  *   mpl_triangulate_rays   lib/multiviews/triangulate.py (the triangulation baseline)
  *   mpl_epipolar_errors    lib/utils/calib.py:94-169 (distance_between_two_skew_lines, smart_pseudo_remove_weight)
+ *   mpl_procrustes_align   lib/utils/pose_utils.py:61-143 (PoseUtils.procrustes, one numpy SVD per pose)
  */
 #ifndef MPL_HIP_H_
 #define MPL_HIP_H_
@@ -387,6 +388,36 @@ int mpl_triangulate_rays(const float *const *rays, const float *const *centers, 
 int mpl_epipolar_errors(const float *const *rays, const float *const *centers, const float *const *conf, int conf_stride,
                         int batch, int views, int joints, float *out_err, const float *weight_in, float threshold,
                         float *weight_out, void *stream);
+
+/* ---- Procrustes alignment of predicted poses onto their targets, csrc/procrustes.hip: the transform behind PA-MPJPE (Protocol
+ * 2), in place of lib/utils/pose_utils.py:61-143 PoseUtils.procrustes (a numpy port of MATLAB's procrustes, one 3x3 SVD per pose
+ * on the host, which would force all_preds back to the host).  One launch aligns `batch` poses: target A and prediction B, both
+ * (batch,joints,3); row vectors as in the reference, Z = scale * B @ R + translation.
+ * Participation: the joints of `sel` (host array of n_sel ints in [0, joints), at most 64, NULL = all joints in order; an entry
+ * listed twice counts twice, as A[sel] would), restricted by `conf` (batch,joints; NULL = all): a joint with conf <= 0 or a
+ * non-finite conf does not take part -- the conf_3d <= 0 mask of evaluate().  scale3 / offset3 (host float[3], NULL = identity):
+ * the room de-normalisation x * scale + offset, applied to BOTH tensors on load (a per-axis scale is no similarity: it has to
+ * happen before the fit); everything below, Z included, is in the de-normalised frame.
+ * Per pose, over the joints that take part (:88-109): A_bar, B_bar the means, A0, B0 the centred points, ssX = sum |A0|^2, ssY =
+ * sum |B0|^2, M = A0^T B0 / sqrt(ssX ssY) = U diag(s) V^T (s descending), R = V U^T, S = sum s.
+ * reflection (:111-119): 0 "best", R as the SVD gives it; 1 forced off: if det R < 0 the last column of V and s[2] change sign;
+ * 2 forced on: the same if det R > 0.  scaling != 0 (:122-130): scale = S sqrt(ssX / ssY); scaling == 0 (:131-134): scale = 1.
+ * In both, aligned = scale * (B - B_bar) R + A_bar for ALL joints of the pose (taking part or not) and translation = A_bar - scale
+ * * B_bar R (:139).  d = sum |Z - A|^2 / ssX over the joints that took part, summed on the points in a second pass: the
+ * reference's 1 - S^2 (:127, :133) is the same number and cancels where the fit is good.
+ * Outputs: aligned (batch,joints,3), d (batch), rotation (batch,3,3) row-major, scale (batch), translation (batch,3); d,
+ * rotation, scale and translation may be NULL, aligned only if d is not.  fp64 arithmetic on the fp32 inputs (the SVD a one-sided
+ * Jacobi on M itself), one rounding into the fp32 outputs, no atomics: identical bits from run to run and from batching to batching.
+ * Degenerate input is a statement about that pose, not an error: fewer than 3 joints taking part, ssX or ssY zero or not finite,
+ * or collinear points (s[1] <= 1e-12 s[0]) make every output of the pose NaN; its neighbours are not affected.
+ * The one deviation: coplanar points (s[2] <= 1e-12 s[0]), where numpy's "best" returns whichever sign its SVD happens to
+ * produce and both fit equally well; here U and V are completed by cross products and R is the proper rotation (det R = +1).
+ * MPL_E_INVALID: pred / target NULL, aligned and d both NULL, a non-positive size, a sel entry outside [0, joints), reflection
+ * outside 0..2; MPL_E_UNSUPPORTED: joints > 64, n_sel > 64, batch * joints > 2^30 -- before any launch.  Like the geometry calls
+ * it neither looks at nor sets the device error word. */
+int mpl_procrustes_align(const float *pred, const float *target, const float *conf, const int *sel, int n_sel,
+                         const float *scale3, const float *offset3, int scaling, int reflection, int batch, int joints,
+                         float *aligned, float *d, float *rotation, float *scale, float *translation, void *stream);
 
 /* ---- output-side epilogue (the step right after the path): what validate() does on the host
  * with `output.clone().cpu().numpy()` -- room de-normalisation x*scale+offset (function_mpl.py:476-488, host float[3]

@@ -18,4 +18,7 @@ def __getattr__(name):
     if name in ("triangulate_rays", "epipolar_errors", "consistency_weights"):
         from . import geometry
         return getattr(geometry, name)
+    if name == "procrustes_align":
+        from .procrustes import procrustes_align
+        return procrustes_align
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

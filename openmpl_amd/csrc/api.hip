@@ -828,6 +828,14 @@ int mpl_epipolar_errors(const float* const* rays, const float* const* centers, c
                                   (hipStream_t)stream);
 }
 
+int mpl_procrustes_align(const float* pred, const float* target, const float* conf, const int* sel, int n_sel, const float* scale3,
+                         const float* offset3, int scaling, int reflection, int batch, int joints, float* aligned, float* d,
+                         float* rotation, float* scale, float* translation, void* stream) {
+    clear_stale_hip_error();
+    return launch_procrustes_align(pred, target, conf, sel, n_sel, scale3, offset3, scaling, reflection, batch, joints, aligned, d,
+                                   rotation, scale, translation, (hipStream_t)stream);
+}
+
 int mpl_pose_metrics_size(int joints) { return 4 + 2 * (joints + 1) + 3 * joints + 3; }
 
 int mpl_pose_metrics(const float* output, const float* target, const float* weight, int batch, int joints,

@@ -4,6 +4,8 @@ Reference: lib/core/function_mpl.py:387-399 (criterion, four `.item()` per batch
 de-normalisation, all_preds / all_gts / all_3d_confs), :612-634 + evaluate() :670-785 (relative and absolute pass, conf_3d mask,
 OUTPUT_IN_METER, per-action breakdown), lib/core/loss.py:39-146 (the criteria).  HIP kernels through the C ABI (mpl_eval_*,
 csrc/evaluate.hip); no CPU path.  update() never synchronises; compute() is the one call that does.
+With aligned="similarity" / "rigid" the run is also scored after a Procrustes alignment of every pose (PA-MPJPE, Protocol 2;
+lib/utils/pose_utils.py:61-143, which nothing in the reference calls): mpl_procrustes_align, csrc/procrustes.hip.
 """
 from __future__ import annotations
 
@@ -16,6 +18,7 @@ from . import cabi
 
 CRITERIA = {"mpjpe": cabi.CRIT_MPJPE, "weighted_mpjpe": cabi.CRIT_WEIGHTED_MPJPE, "l1": cabi.CRIT_L1, "mse": cabi.CRIT_MSE,
             "mpjpe_kadkhoda": cabi.CRIT_MPJPE_KADKHODA}
+ALIGNED = {None: None, "similarity": True, "rigid": False}         # -> scaling of procrustes_align
 
 
 def _wrap(indices, n, what):
@@ -43,13 +46,21 @@ class PoseEvaluator:
     joints: the selection `u` of `all_preds[:, u, :]` (default: all joints in order; entry 0 is the root of the relative pass).
     groups: the largest class id (Human3.6M actions: 16): a sample with id 1..groups is also scored in its own class.
     output_in_meter: DATASET.OUTPUT_IN_METER.  not_consider_kp: SELECTED joints deleted from mpjpe (np.delete semantics).
-    keep_poses: capacity, in samples, of the device copy of all_preds / all_gts (0: none is kept)."""
+    keep_poses: capacity, in samples, of the device copy of all_preds / all_gts (0: none is kept).
+    aligned: None, "similarity" or "rigid": also score every pose after PoseUtils.procrustes(target, output, scaling = True /
+    False, reflection="best") over the selected joints whose conf_3d is > 0, in the de-normalised frame (PA-MPJPE): compute()
+    gains "aligned".  A pose whose alignment is degenerate (fewer than 3 joints left, all points equal, collinear points) is NaN
+    there, which the nan-aware sums skip joint by joint, exactly as they skip a masked joint: it adds 0 to pjpe and nothing to
+    dist, and still counts in n_samples.  None (the default) changes nothing: state, launches and results are as without it."""
 
     def __init__(self, num_joints: int, criterion: str = "mpjpe", weight_axis: Optional[Sequence[float]] = None,
                  joints: Optional[Sequence[int]] = None, groups: Optional[int] = None, output_in_meter: bool = False,
-                 not_consider_kp: Optional[Sequence[int]] = None, keep_poses: int = 0, device=None):
+                 not_consider_kp: Optional[Sequence[int]] = None, keep_poses: int = 0, device=None, aligned: Optional[str] = None):
         if criterion not in CRITERIA:
             raise ValueError("criterion must be one of %s" % ", ".join(sorted(CRITERIA)))
+        if not (aligned is None or isinstance(aligned, str)) or aligned not in ALIGNED:
+            raise ValueError("aligned must be None, 'similarity' or 'rigid' (got %r)" % (aligned,))
+        self.aligned = aligned
         J = int(num_joints)
         if not 1 <= J <= 64:
             raise NotImplementedError("1 <= num_joints <= 64")
@@ -84,6 +95,20 @@ class PoseEvaluator:
             raise NotImplementedError("mpl_eval_state_bytes refused (n_sel %d, n_groups %d)" % (S, self.n_groups))
         self.keep_poses = int(keep_poses)
         self._alloc(nbytes)
+        self._state_aligned = None
+        if aligned is not None:
+            # the aligned poses are scored by a second, separate state: plain MPJPE on poses that are de-normalised already
+            self._opt_aligned = cabi.EvalOptions()
+            self._opt_aligned.criterion = cabi.CRIT_MPJPE
+            self._opt_aligned.weight_axis[:] = [1.0] * 3
+            self._opt_aligned.scale[:] = [1.0] * 3
+            self._opt_aligned.offset[:] = [0.0] * 3
+            self._opt_aligned.metre_factor = self._opt.metre_factor
+            self._opt_aligned.n_views = 1
+            self._opt_aligned.n_sel, self._opt_aligned.n_groups = S, self.n_groups
+            for i, j in enumerate(self.sel):
+                self._opt_aligned.sel[i] = j
+            self._alloc_aligned(nbytes)
         self.reset()
 
     def _alloc(self, nbytes):
@@ -92,12 +117,19 @@ class PoseEvaluator:
         self._keep = torch.zeros((2, self.keep_poses, self.num_joints, 3), dtype=torch.float32, device=self.device) \
             if self.keep_poses > 0 else None
 
+    def _alloc_aligned(self, nbytes):
+        """State of the aligned pass (only with aligned=...; the tests' hook like _alloc)."""
+        self._state_aligned = torch.empty(nbytes // 8, dtype=torch.float64, device=self.device)
+
     def _stream(self):
         return torch.cuda.current_stream(self.device).cuda_stream
 
     def reset(self):
         with torch.cuda.device(self.device):
             cabi.check(self._lib.mpl_eval_reset(self._state.data_ptr(), len(self.sel), self.n_groups, self._stream()), "mpl_eval_reset")
+            if self._state_aligned is not None:
+                cabi.check(self._lib.mpl_eval_reset(self._state_aligned.data_ptr(), len(self.sel), self.n_groups, self._stream()),
+                           "mpl_eval_reset")
         self._fed = 0
 
     def _pose(self, t, shape, what):
@@ -113,7 +145,8 @@ class PoseEvaluator:
         """One batch, on the current stream, without any host synchronisation.  output: (B,J,3) float32, or the kadkhod tuple
         (poses, [x1, x2]) as the model returns it; target (B,J,3); weight (B,J) or (B,J,1); conf_3d (B,J) or (B,J,1): joints with
         conf_3d <= 0 are masked (indexed through the joint selection like the poses); group (B,) int32 class ids;
-        scale / offset: room de-normalisation, a number or 3 values; n_views: len(input), the AverageMeter weight."""
+        scale / offset: room de-normalisation, a number or 3 values; n_views: len(input), the AverageMeter weight.
+        With aligned=..., the poses (of the kadkhod tuple: the final ones) are also aligned to their targets and scored."""
         x1 = x2 = None
         if isinstance(output, (tuple, list)):
             output, inter = output
@@ -175,22 +208,46 @@ class PoseEvaluator:
                                                None if self._keep is None else self._keep[0].data_ptr(),
                                                None if self._keep is None else self._keep[1].data_ptr(), self.keep_poses, self._stream())
         cabi.check(rc, "mpl_eval_accumulate")
+        if self._state_aligned is not None:
+            self._update_aligned(output, target, conf_3d, group, B, J)
         self._fed += B
 
-    def _report(self) -> torch.Tensor:
+    def _update_aligned(self, output, target, conf_3d, group, B, J):
+        """Align the batch to its targets with the selection, conf_3d and de-normalisation of this call (temporaries from the
+        caching allocator, no host synchronisation) and accumulate it against the de-normalised targets."""
+        from . import procrustes
+        sc, of = list(self._opt.scale), list(self._opt.offset)
+        z = torch.empty_like(output)
+        d = torch.empty((B,), dtype=torch.float32, device=self.device)
+        procrustes._launch(output, target, conf_3d, self.sel, ALIGNED[self.aligned], cabi.REFLECT_BEST, sc, of, B, J, z, d, None, None, None)
+        if sc != [1.0] * 3 or of != [0.0] * 3:
+            tgt = torch.empty_like(target)              # x * scale + offset per axis, as the kernels de-normalise (Python scalars:
+            for a in range(3):                          # no host-to-device copy)
+                torch.mul(target[..., a], sc[a], out=tgt[..., a]).add_(of[a])
+            target = tgt
+        with torch.cuda.device(self.device):
+            rc = self._lib.mpl_eval_accumulate(self._state_aligned.data_ptr(), C.byref(self._opt_aligned), z.data_ptr(), None, None,
+                                               target.data_ptr(), None, None if conf_3d is None else conf_3d.data_ptr(),
+                                               None if group is None else group.data_ptr(), B, J, None, None, 0, self._stream())
+        cabi.check(rc, "mpl_eval_accumulate")
+
+    def _report(self, state=None) -> torch.Tensor:
         """The raw report on the device (stream-ordered, no synchronisation)."""
         S = len(self.sel)
+        state = self._state if state is None else state
         rep = torch.empty(self._lib.mpl_eval_report_size(S, self.n_groups), dtype=torch.float64, device=self.device)
         with torch.cuda.device(self.device):
-            cabi.check(self._lib.mpl_eval_report(self._state.data_ptr(), S, self.n_groups, self.skip_mask, rep.data_ptr(), self._stream()),
+            cabi.check(self._lib.mpl_eval_report(state.data_ptr(), S, self.n_groups, self.skip_mask, rep.data_ptr(), self._stream()),
                        "mpl_eval_report")
         return rep
 
     def compute(self) -> Dict:
         """What validate() logs and evaluate() returns, as numpy float64: {"relative": ..., "absolute": ...} each with pjpe (S),
         mpjpe, dist (S,3), dist_mean (3), n_samples and per_group {id: the same fields} (empty groups omitted, as the reference
-        skips actions without samples); loss, loss_axis (3), n_samples.  The one call that synchronises."""
+        skips actions without samples); loss, loss_axis (3), n_samples.  With aligned=..., also "aligned": the fields of the
+        absolute pass on the Procrustes-aligned poses (PA-MPJPE).  The one call that synchronises."""
         S, G = len(self.sel), self.n_groups
+        ra = self._report(self._state_aligned) if self._state_aligned is not None else None
         r = self._report().cpu().numpy()
         # NaN poses of a failed forward would be skipped by nansum / nanmean: a poisoned state reports NaN, and a failure that is
         # still pending raises here, with the results it spoiled
@@ -207,6 +264,11 @@ class PoseEvaluator:
             e = fields(blocks[0])
             e["per_group"] = {g: fields(blocks[g]) for g in range(1, G) if blocks[g][4 * S + 4] > 0}
             out[name] = e
+        if ra is not None:
+            ra = ra.cpu().numpy()
+            blocks = [ra[8 + g * w:8 + (g + 1) * w] for g in range(G)]
+            out["aligned"] = fields(blocks[0])
+            out["aligned"]["per_group"] = {g: fields(blocks[g]) for g in range(1, G) if blocks[g][4 * S + 4] > 0}
         return out
 
     def poses(self):
