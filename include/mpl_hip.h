@@ -28,6 +28,7 @@
  *   mpl_triangulate_rays   lib/multiviews/triangulate.py (the triangulation baseline)
  *   mpl_epipolar_errors    lib/utils/calib.py:94-169 (distance_between_two_skew_lines, smart_pseudo_remove_weight)
  *   mpl_procrustes_align   lib/utils/pose_utils.py:61-143 (PoseUtils.procrustes, one numpy SVD per pose)
+ *   mpl_synthesize_views   lib/dataset/multiview_amass_h36m_mpl.py:317-342 + joints_dataset_mpl.py:588-774 (synthetic detections)
  */
 #ifndef MPL_HIP_H_
 #define MPL_HIP_H_
@@ -361,6 +362,56 @@ int mpl_linear(const float *xa, int Ka, const float *xb, int Kb, int M, const fl
 int mpl_prepare_inputs(const float *joints_px, const float *conf, const double *cams_dev, int batch, int views,
                        int joints, float img_w, float img_h, int normalize_inputs, int normalize_cameras,
                        float *const *poses, float *const *rays, float *const *centers, void *stream);
+
+/* ---- synthesis of the multi-view model inputs from 3D poses, csrc/synth.hip: the producer in front of mpl_prepare_inputs, in
+ * place of what the reference's synthetic datasets run in numpy per sample and view inside Dataset.__getitem__:
+ * lib/dataset/multiview_amass_h36m_mpl.py:317-342 (pose placement), lib/utils/calib.py:42-77 (projection),
+ * lib/dataset/joints_dataset_mpl.py:592-613 (detection noise, confidence penalty), :701-727 (visibility under NO_AUGMENTATION),
+ * :735-740 (missing joints), then :762-774, :615-623, :872-904 exactly as mpl_prepare_inputs.  One launch, one work item per
+ * (pose, view, joint); fp64 arithmetic on the fp32 tensors, one rounding per output, no atomics: identical bits from run to run.
+ * Steps, per item: 1. X = pose @ Rz(angle)^T about the world origin (rotation_deg, or opt->rotate: 360 * draw), then + the
+ * translation (all three components of `translation`, or opt->room: (min + draw * (max - min)) in x and y);  2. x_cam = R (X - t),
+ * px = (fx x / z + cx, fy y / z + cy) -> pixels_clean, depth = z;  3. if noise_level != 0: px += noise_level * n, n a
+ * standard-normal pair, conf *= penalty(|noise_level * n|): MPL_SYNTH_PENALIZE_EXP_ERROR a exp(-b d), _LINEAR a d + b,
+ * _EXP_SQRT exp(-d / 2);  4. clip != 0: conf = 0 unless 0 < x < w-1 and 0 < y < h-1, then x, y clamped to [0, w-1], [0, h-1];
+ * clip == 0: conf = 0 where min(x, y) < 0, x >= w or y >= h, and px = (0,0) wherever conf <= 0;  5. if missing_level > 0: conf
+ * and px times 0 where a uniform draw < missing_level -> pixels;  6. poses / rays / centers from that fp64 pixel with the
+ * arithmetic and the normalize_* switches of mpl_prepare_inputs;  7. target = (X - target_offset) / target_scale per axis.
+ * The one deviation: a joint at z <= 1e-9, where the reference divides anyway, gets conf 0 and px (0,0) in pixels_clean and
+ * pixels and skips steps 3 to 5.
+ * Random numbers: draw i of a stream is the top 53 bits of SplitMix64's finaliser of key + (i + 1) * 0x9E3779B97F4A7C15, a double
+ * in [0,1) (openmpl_amd/detrng.py, which also derives the keys).  key_rot, key_room_x, key_room_y are indexed by first_index + b;
+ * key_noise0, key_noise1, key_missing by ((first_index + b) * views + v) * joints + j: a run cut into batches draws what the uncut
+ * run draws.  The normal pair is Box-Muller: u1 = 1 - draw(key_noise0), u2 = draw(key_noise1), r = sqrt(-2 ln u1),
+ * n = (r cos 2 pi u2, r sin 2 pi u2).  A non-NULL rotation_deg (B), translation (B,3), noise (B,V,J,2; standard normal, before the
+ * noise_level factor) or missing_u (B,V,J) replaces the stream of that step; a step that is off reads and draws nothing.
+ * poses3d (B,J,3), conf (B,V,J) or NULL (-> 1): device fp32;  cams_dev: as for mpl_prepare_inputs.  Outputs: poses / rays /
+ * centers host arrays of V device pointers (all three or all NULL), target (B,J,3), pixels, pixels_clean (B,V,J,2), depth (B,V,J),
+ * each nullable, at least one given.
+ * MPL_E_INVALID: poses3d, cams_dev or opt NULL, no output, a non-positive size, views > MPL_MAX_VIEWS, img_w or img_h <= 0, a
+ * target_scale component that is 0, a penalize outside 0..3; MPL_E_UNSUPPORTED: batch * views * joints > 2^36 -- before any
+ * launch.  Like the geometry calls it neither looks at nor sets the device error word. */
+#define MPL_SYNTH_PENALIZE_NONE 0
+#define MPL_SYNTH_PENALIZE_EXP_ERROR 1
+#define MPL_SYNTH_PENALIZE_LINEAR 2
+#define MPL_SYNTH_PENALIZE_EXP_SQRT 3
+typedef struct mpl_synth_options {
+    int32_t penalize;                          /* MPL_SYNTH_PENALIZE_* */
+    int32_t clip;                              /* DATASET.CLIP_JOINTS */
+    int32_t rotate, room;                      /* draw the rotation / the room translation (ignored where a tensor is given) */
+    int32_t normalize_inputs, normalize_cameras;
+    double noise_level, missing_level;         /* NOISE_LEVEL in pixels (0 = step 3 off), MISSING_LEVEL (<= 0 = step 5 off) */
+    double penalize_a, penalize_b;
+    double room_min_x, room_max_x, room_min_y, room_max_y;
+    double img_w, img_h;                       /* NETWORK.IMAGE_SIZE */
+    double target_scale[3], target_offset[3];
+    uint64_t key_rot, key_room_x, key_room_y, key_noise0, key_noise1, key_missing;
+    int64_t first_index;                       /* global index of pose 0 of this call */
+} mpl_synth_options;
+int mpl_synthesize_views(const float *poses3d, const double *cams_dev, const mpl_synth_options *opt, const float *conf,
+                         const float *rotation_deg, const float *translation, const float *noise, const float *missing_u,
+                         int batch, int views, int joints, float *const *poses, float *const *rays, float *const *centers,
+                         float *target, float *pixels, float *pixels_clean, float *depth, void *stream);
 
 /* ---- multi-view geometry on the tensors of mpl_inputs, csrc/geometry.hip: rays[v] (B,J,3) is a world point on the line of
  * sight of view v (joints_dataset_mpl.py:872-904), centers[v] (B,1,3) the camera centre; line v goes through c_v along

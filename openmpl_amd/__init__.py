@@ -21,4 +21,7 @@ def __getattr__(name):
     if name == "procrustes_align":
         from .procrustes import procrustes_align
         return procrustes_align
+    if name in ("synthesize_views", "project_points"):
+        from . import synth
+        return getattr(synth, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

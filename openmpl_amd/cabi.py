@@ -92,6 +92,20 @@ class EvalOptions(C.Structure):
                 ("n_groups", C.c_int32), ("sel", C.c_uint8 * 64)]
 
 
+# mpl_synthesize_views(): the confidence penalties (MPL_SYNTH_PENALIZE_* of mpl_hip.h) and the options struct
+SYNTH_PENALIZE = {"none": 0, "exp_error": 1, "linear": 2, "exp_sqrt": 3}
+
+
+class SynthOptions(C.Structure):
+    _fields_ = [("penalize", C.c_int32), ("clip", C.c_int32), ("rotate", C.c_int32), ("room", C.c_int32),
+                ("normalize_inputs", C.c_int32), ("normalize_cameras", C.c_int32),
+                ("noise_level", C.c_double), ("missing_level", C.c_double), ("penalize_a", C.c_double), ("penalize_b", C.c_double),
+                ("room_min_x", C.c_double), ("room_max_x", C.c_double), ("room_min_y", C.c_double), ("room_max_y", C.c_double),
+                ("img_w", C.c_double), ("img_h", C.c_double), ("target_scale", C.c_double * 3), ("target_offset", C.c_double * 3),
+                ("key_rot", C.c_uint64), ("key_room_x", C.c_uint64), ("key_room_y", C.c_uint64), ("key_noise0", C.c_uint64),
+                ("key_noise1", C.c_uint64), ("key_missing", C.c_uint64), ("first_index", C.c_int64)]
+
+
 class Inputs(C.Structure):
     _fields_ = [("batch", C.c_int32), ("reserved", C.c_int32),
                 ("poses", _fp * MPL_MAX_VIEWS), ("rays", _fp * MPL_MAX_VIEWS), ("centers", _fp * MPL_MAX_VIEWS)]
@@ -100,7 +114,7 @@ class Inputs(C.Structure):
 EXPORTS = ("mpl_hip_abi_version", "mpl_hip_error_string", "mpl_config_supported", "mpl_fpt_width", "mpl_forward_workspace_bytes",
            "mpl_forward", "mpl_spt_tokens", "mpl_block_stack_workspace_bytes", "mpl_block_stack", "mpl_block_stack_ex",
            "mpl_ln_linear", "mpl_spt_pack_bytes", "mpl_spt_pack", "mpl_d32_pack", "mpl_pack_bf16_bytes", "mpl_pack_bf16", "mpl_bf16_operand_layout", "mpl_pack_bf16_any_bytes", "mpl_pack_bf16_any", "mpl_ln_linear_bf16_any_workspace_bytes", "mpl_ln_linear_bf16_any", "mpl_pack_h2_bytes", "mpl_pack_h2", "mpl_pack_h2_scaled", "mpl_pack_h2_out_scale", "mpl_ln_linear_h2_workspace_bytes", "mpl_ln_linear_h2", "mpl_x3_debug_buffer", "mpl_x3_stack_mode", "mpl_block_stack_form", "mpl_block_stack_form_ex", "mpl_block_stack_last_form", "mpl_spt_form", "mpl_device_error", "mpl_device_error_clear", "mpl_x3_spin_limit", "mpl_token_attention", "mpl_fuse_head", "mpl_view_fuse", "mpl_view_norm",
-           "mpl_layernorm", "mpl_linear", "mpl_pose_metrics_size", "mpl_pose_metrics", "mpl_pose_metrics_ex", "mpl_eval_state_bytes", "mpl_eval_reset", "mpl_eval_accumulate", "mpl_eval_report_size", "mpl_eval_report", "mpl_prepare_inputs", "mpl_triangulate_rays", "mpl_epipolar_errors", "mpl_procrustes_align", "mpl_profile_start",
+           "mpl_layernorm", "mpl_linear", "mpl_pose_metrics_size", "mpl_pose_metrics", "mpl_pose_metrics_ex", "mpl_eval_state_bytes", "mpl_eval_reset", "mpl_eval_accumulate", "mpl_eval_report_size", "mpl_eval_report", "mpl_prepare_inputs", "mpl_synthesize_views", "mpl_triangulate_rays", "mpl_epipolar_errors", "mpl_procrustes_align", "mpl_profile_start",
            "mpl_profile_stop")
 KINDS = ("spt", "row_stats", "gemm", "attention", "fuse_head", "pack")
 
@@ -250,6 +264,9 @@ def load():
         lib.mpl_prepare_inputs.restype = C.c_int
         lib.mpl_prepare_inputs.argtypes = [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int,
                                            C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_fp), _fp]
+        lib.mpl_synthesize_views.restype = C.c_int
+        lib.mpl_synthesize_views.argtypes = [_fp, _fp, C.POINTER(SynthOptions), _fp, _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int,
+                                             C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_fp), _fp, _fp, _fp, _fp, _fp]
         lib.mpl_triangulate_rays.restype = C.c_int
         lib.mpl_triangulate_rays.argtypes = [C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_fp), C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp,
                                              _fp]

@@ -814,6 +814,15 @@ int mpl_prepare_inputs(const float* joints_px, const float* conf, const double* 
                                  normalize_cameras, poses, rays, centers, (hipStream_t)stream);
 }
 
+int mpl_synthesize_views(const float* poses3d, const double* cams_dev, const mpl_synth_options* opt, const float* conf,
+                         const float* rotation_deg, const float* translation, const float* noise, const float* missing_u, int batch,
+                         int views, int joints, float* const* poses, float* const* rays, float* const* centers, float* target,
+                         float* pixels, float* pixels_clean, float* depth, void* stream) {
+    clear_stale_hip_error();
+    return launch_synthesize_views(poses3d, cams_dev, opt, conf, rotation_deg, translation, noise, missing_u, batch, views, joints,
+                                   poses, rays, centers, target, pixels, pixels_clean, depth, (hipStream_t)stream);
+}
+
 int mpl_triangulate_rays(const float* const* rays, const float* const* centers, const float* const* conf, int conf_stride, int batch,
                          int views, int joints, float* out_points, float* out_residual, void* stream) {
     clear_stale_hip_error();

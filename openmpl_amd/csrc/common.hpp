@@ -330,6 +330,12 @@ int launch_triangulate_rays(const float* const* rays, const float* const* center
 int launch_epipolar_errors(const float* const* rays, const float* const* centers, const float* const* conf, int conf_stride, int B,
                            int V, int J, float* err, const float* weight_in, float threshold, float* weight_out, hipStream_t s);
 
+// synth.hip: model inputs synthesized from 3D poses (mpl_synthesize_views)
+int launch_synthesize_views(const float* poses3d, const double* cams_dev, const mpl_synth_options* opt, const float* conf,
+                            const float* rotation_deg, const float* translation, const float* noise, const float* missing_u,
+                            int B, int V, int J, float* const* poses, float* const* rays, float* const* centers, float* target,
+                            float* pixels, float* pixels_clean, float* depth, hipStream_t s);
+
 // procrustes.hip: similarity / rigid alignment of predicted poses onto their targets (mpl_procrustes_align)
 int launch_procrustes_align(const float* pred, const float* target, const float* conf, const int* sel, int n_sel, const float* scale3,
                             const float* offset3, int scaling, int reflection, int B, int J, float* aligned, float* d,
