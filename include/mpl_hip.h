@@ -27,6 +27,7 @@
  *   mpl_fuse_head          forward_features tail :425-446 + default head :283-286,:521-523
  *   mpl_triangulate_rays   lib/multiviews/triangulate.py (the triangulation baseline)
  *   mpl_epipolar_errors    lib/utils/calib.py:94-169 (distance_between_two_skew_lines, smart_pseudo_remove_weight)
+ *   mpl_triangulate_robust lib/multiviews/triangulate.py:88-112 (view selection by confidence) + pair consensus
  *   mpl_procrustes_align   lib/utils/pose_utils.py:61-143 (PoseUtils.procrustes, one numpy SVD per pose)
  *   mpl_synthesize_views   lib/dataset/multiview_amass_h36m_mpl.py:317-342 + joints_dataset_mpl.py:588-774 (synthetic detections)
  */
@@ -439,6 +440,30 @@ int mpl_triangulate_rays(const float *const *rays, const float *const *centers, 
 int mpl_epipolar_errors(const float *const *rays, const float *const *centers, const float *const *conf, int conf_stride,
                         int batch, int views, int joints, float *out_err, const float *weight_in, float threshold,
                         float *weight_out, void *stream);
+/* mpl_triangulate_robust: mpl_triangulate_rays with the outliers taken out first, per (sample, joint) in three stages.
+ * 1. Candidates: the views that take part (w_v > 0 and finite).  conf_threshold >= 0 (a negative or NaN value: off) adds the
+ * view selection of lib/multiviews/triangulate.py:94-102 over all `views` confidences in fp64, literally: th = conf_threshold;
+ * loop { sel = conf > th; if th < -1 stop; if |sel| <= 1 then th -= 0.05 (repeated subtraction: the reference's thresholds bit
+ * for bit) else stop }; the candidates are sel without the views that do not take part.  Two deviations: below th = 0 the
+ * reference would select zero-confidence views, here they stay out; and the reference never resets th between the joints of a
+ * pose (a joint inherits what an earlier one lowered), here every joint starts at conf_threshold.
+ * 2. Consensus, with threshold >= 0 (tau in world units; negative or NaN: off): every candidate pair i < k is a hypothesis, the
+ * equal-weight least-squares point of the two lines (the midpoint of their common perpendicular), solved about the mean of the
+ * two centres and skipped where det(A / 2) < 1e-10.  A hypothesis counts the candidates with dist(x, line_v) <= tau and costs
+ * sum over the candidates of w_v min(dist^2, tau^2); the winner is the highest count, then the lowest cost, then the lowest i,
+ * then the lowest k -- a total order, so the result does not depend on how the pairs were dealt out.  Its dist <= tau set is the
+ * inlier set.  Without threshold every candidate is an inlier.
+ * 3. Refit: out_points / out_residual are those of mpl_triangulate_rays with the weights w_v over the inlier set (cbar stays the
+ * mean of all `views` centres).  With both stages off the call writes what mpl_triangulate_rays writes.
+ * out_inliers (B,V,J), the layout of out_err: 1 for the views of the inlier set, else 0.  Fewer than two candidates, no
+ * non-degenerate pair, a winning count below min_inliers, or a degenerate refit are statements about the joint: its point and
+ * residual are NaN and its inliers all 0; a finite point has at least two inliers.  One launch; pairs are dealt to the waves of
+ * a workgroup that holds the lines of 64 items in LDS.
+ * Besides the codes above, MPL_E_INVALID: a NULL output, conf_threshold on without conf, min_inliers outside [2, views];
+ * MPL_E_UNSUPPORTED: conf_threshold > 64 (the descent is a loop in every thread) -- before any launch. */
+int mpl_triangulate_robust(const float *const *rays, const float *const *centers, const float *const *conf, int conf_stride,
+                           int batch, int views, int joints, double threshold, double conf_threshold, int min_inliers,
+                           float *out_points, float *out_residual, float *out_inliers, void *stream);
 
 /* ---- Procrustes alignment of predicted poses onto their targets, csrc/procrustes.hip: the transform behind PA-MPJPE (Protocol
  * 2), in place of lib/utils/pose_utils.py:61-143 PoseUtils.procrustes (a numpy port of MATLAB's procrustes, one 3x3 SVD per pose

@@ -15,7 +15,7 @@ def __getattr__(name):
     if name == "PoseEvaluator":
         from .evaluate import PoseEvaluator
         return PoseEvaluator
-    if name in ("triangulate_rays", "epipolar_errors", "consistency_weights"):
+    if name in ("triangulate_rays", "triangulate_rays_robust", "epipolar_errors", "consistency_weights"):
         from . import geometry
         return getattr(geometry, name)
     if name == "procrustes_align":

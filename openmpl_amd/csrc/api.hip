@@ -837,6 +837,14 @@ int mpl_epipolar_errors(const float* const* rays, const float* const* centers, c
                                   (hipStream_t)stream);
 }
 
+int mpl_triangulate_robust(const float* const* rays, const float* const* centers, const float* const* conf, int conf_stride, int batch,
+                           int views, int joints, double threshold, double conf_threshold, int min_inliers, float* out_points,
+                           float* out_residual, float* out_inliers, void* stream) {
+    clear_stale_hip_error();
+    return launch_triangulate_robust(rays, centers, conf, conf_stride, batch, views, joints, threshold, conf_threshold, min_inliers,
+                                     out_points, out_residual, out_inliers, (hipStream_t)stream);
+}
+
 int mpl_procrustes_align(const float* pred, const float* target, const float* conf, const int* sel, int n_sel, const float* scale3,
                          const float* offset3, int scaling, int reflection, int batch, int joints, float* aligned, float* d,
                          float* rotation, float* scale, float* translation, void* stream) {

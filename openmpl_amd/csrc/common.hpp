@@ -324,11 +324,15 @@ int launch_prepare_inputs(const float* px, const float* conf, const double* cams
                           int norm_in, int norm_cam, float* const* poses, float* const* rays, float* const* centers,
                           hipStream_t s);
 
-// geometry.hip: triangulation of the model's rays and the epipolar consistency score (mpl_triangulate_rays, mpl_epipolar_errors)
+// geometry.hip: triangulation of the model's rays and the epipolar consistency score (mpl_triangulate_rays, mpl_epipolar_errors,
+// mpl_triangulate_robust)
 int launch_triangulate_rays(const float* const* rays, const float* const* centers, const float* const* conf, int conf_stride, int B,
                             int V, int J, float* points, float* residual, hipStream_t s);
 int launch_epipolar_errors(const float* const* rays, const float* const* centers, const float* const* conf, int conf_stride, int B,
                            int V, int J, float* err, const float* weight_in, float threshold, float* weight_out, hipStream_t s);
+int launch_triangulate_robust(const float* const* rays, const float* const* centers, const float* const* conf, int conf_stride, int B,
+                              int V, int J, double threshold, double conf_threshold, int min_inliers, float* points,
+                              float* residual, float* inliers, hipStream_t s);
 
 // synth.hip: model inputs synthesized from 3D poses (mpl_synthesize_views)
 int launch_synthesize_views(const float* poses3d, const double* cams_dev, const mpl_synth_options* opt, const float* conf,

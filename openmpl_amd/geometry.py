@@ -6,6 +6,8 @@ distance_between_two_skew_lines and :116-169 smart_pseudo_remove_weight (numpy, 
 of V (B,1,3) camera centres -- what prepare_inputs returns and `model(input, centers=centers, rays=rays)` takes.  `conf` is a list of
 V tensors, each (B,J) or one of the model's own (B,J,3) pose tensors, whose channel 2 is read in place.  Two HIP kernels through the
 C ABI (mpl_triangulate_rays, mpl_epipolar_errors, csrc/geometry.hip) on the current stream; no synchronisation, no CPU path.
+triangulate_rays_robust (mpl_triangulate_robust, a third kernel) puts the view selection of lib/multiviews/triangulate.py:88-112
+and a pair consensus in front of the same least-squares fit.
 """
 from __future__ import annotations
 
@@ -84,6 +86,54 @@ def triangulate_rays(rays: Sequence[torch.Tensor], centers: Sequence[torch.Tenso
                                       residual.data_ptr(), torch.cuda.current_stream().cuda_stream)
     cabi.check(rc, "mpl_triangulate_rays")
     return points, residual
+
+
+def triangulate_rays_robust(rays: Sequence[torch.Tensor], centers: Sequence[torch.Tensor],
+                            conf: Optional[Sequence[torch.Tensor]] = None, threshold: Optional[float] = None,
+                            conf_threshold: Optional[float] = None, min_inliers: int = 2
+                            ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """triangulate_rays with the outliers taken out first: (points (B,J,3), residual (B,J), inliers (B,V,J) of 0 / 1; the layout
+    of epipolar_errors, so inliers.unbind(1) is a conf or a weight list).  Per (sample, joint), in this order:
+
+    1. candidates: the views that take part (conf > 0 and finite).  With `conf_threshold` (conf required) the reference's rule
+       (triangulate.py:94-102) selects among all V confidences: th = conf_threshold; while at most one conf > th and th >= -1:
+       th -= 0.05.  Two deviations: below th = 0 the reference would select zero-confidence views, here they stay out; and every
+       joint starts at conf_threshold, where the reference hands a lowered threshold on to the later joints of the pose.
+    2. consensus, with `threshold` (tau, world units): every candidate pair is a hypothesis, the midpoint of the common
+       perpendicular of its two lines; the winner has the most candidates within tau, then the lowest sum of conf * min(dist^2,
+       tau^2), then the lowest pair.  Its within-tau set is the inlier set; without `threshold` every candidate is an inlier.
+    3. refit: the point and residual of triangulate_rays over the inlier set.
+
+    Fewer than two candidates, no pair further than about 2e-5 rad from parallel, a winner with fewer than `min_inliers` views
+    within tau, or a degenerate refit make the joint NaN in points and residual and its inliers all 0.  With threshold=None and
+    conf_threshold=None this is triangulate_rays.  One launch, no synchronisation, identical bits from run to run and from
+    batching to batching."""
+    V = len(_listed(rays, "rays"))
+    tau = cth = -1.0                                     # the C ABI's "off"
+    if threshold is not None:
+        tau = float(threshold)
+        if not tau > 0.0:
+            raise RuntimeError("threshold must be a positive distance in world units (got %r)" % (threshold,))
+    if conf_threshold is not None:
+        cth = float(conf_threshold)
+        if cth != cth or cth > 64.0:
+            raise RuntimeError("conf_threshold must be a number of at most 64 (got %r)" % (conf_threshold,))
+        if conf is None:
+            raise RuntimeError("conf_threshold needs conf")
+    if int(min_inliers) != min_inliers or not 2 <= min_inliers <= V:
+        raise RuntimeError("min_inliers must be an integer in [2, %d views] (got %r)" % (V, min_inliers))
+    rays, centers, conf, _, stride, B, V, J = _lines(rays, centers, conf)
+    dev = rays[0].device
+    lib = cabi.load()
+    points = torch.empty((B, J, 3), dtype=torch.float32, device=dev)
+    residual = torch.empty((B, J), dtype=torch.float32, device=dev)
+    inliers = torch.empty((B, V, J), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.mpl_triangulate_robust(_table(rays), _table(centers), _table(conf), stride, B, V, J, tau, cth, int(min_inliers),
+                                        points.data_ptr(), residual.data_ptr(), inliers.data_ptr(),
+                                        torch.cuda.current_stream().cuda_stream)
+    cabi.check(rc, "mpl_triangulate_robust")
+    return points, residual, inliers
 
 
 def _epipolar(rays, centers, conf, weight, threshold):
