@@ -268,11 +268,35 @@ __device__ __forceinline__ bool h2_att_in_registers(int ntok, int hd, int rpt) {
     return (ntok == 2 || ntok == 4 || ntok == 8) && (hd == 68 || hd == BN) && rpt == BM;
 }
 
-template <int EPI, bool LNF, int NPASS, int NTW, bool CHAIN, int WC, int RT = 1, int NP = 2, bool ACT = true, bool DW = false>
+// Cross-phase W prefetch (PF: the phases of h2_stack_kernel -- RT = 1, CHAIN, whole tiles).  The last DIST stages of a phase have
+// nothing left to request, and the next phase used to start on an empty ring: W(0), the hand-off, then 5 x 26 KiB before its
+// first barrier period could multiply.  W depends on nothing a partner writes, so the tail stage with REM stages left requests
+// the W pieces of the NEXT phase's stage DIST - REM -- into the slot it would refill if its own phase went on (the slot of stage
+// t - 1, free since the barrier in front of stage t - 1), each wave the pieces it would have requested in the next prologue.
+// The next phase's stage j therefore lives in ring slot (base + T + j) mod NST: the ring base rotates from phase to phase
+// (`base`), and a phase entered with `pre` skips the W requests of its prologue (all else -- A, the statistics rows, the
+// epilogue vectors, the bookkeeping of issue_w -- as before).  The store drain at the end of a phase waits for every request of
+// the wave and the barrier behind it publishes them, so the prefetched pieces have landed before the next phase starts:
+// its first counted wait only covers what that phase requested itself.
+struct H2Pf {
+    unsigned base;        // byte offset (a multiple of the stage size) of the ring slot of this phase's stage 0
+    int pre;              // the W pieces of this phase's stages 0 .. DIST - 1 were requested by the previous phase
+    const char* nw;       // next phase: pass 0 of the W stream of this workgroup's column group (NULL: nothing to prefetch)
+    unsigned pstride;     // bytes from one pass of that stream to the next
+    int npass;
+};
+// Shortest phase (stages) that is entered prefetched: the counted waits of the tail stages that still request (REM > DIST) allow
+// the requests of the stages t + 2 .. t + 4 in flight, counted as W pieces of this phase -- true from stage 3 on, and a phase of
+// 12 stages or more starts its tail (at most 9 stages) no earlier.  (D = 544: every phase but the 9-stage proj of the bf16 engine.)
+constexpr int H2_PF_MIN_T = 12;
+
+template <int EPI, bool LNF, int NPASS, int NTW, bool CHAIN, int WC, int RT = 1, int NP = 2, bool ACT = true, bool DW = false, bool PF = false>
 __device__ __forceinline__ bool h2_phase(const H2Args& a, char* smem, int tid, int wave, int slot0, int tm, int tn,
-                                         unsigned* chain, unsigned chain_need, bool arrive = true, int rg_lo = 0, int rgs = 4) {
+                                         unsigned* chain, unsigned chain_need, bool arrive = true, int rg_lo = 0, int rgs = 4,
+                                         H2Pf* pf = nullptr) {
     static_assert(ACT || (RT == 1 && CHAIN), "loader-only waves exist in the row-narrow stack only");
     static_assert(!DW || (RT == 1 && CHAIN && NP == 2), "direct-W form: 16-row teams of the fp16x2 stack");
+    static_assert(!PF || (RT == 1 && CHAIN && ACT && !DW), "cross-phase W prefetch: the whole-tile chain form only");
     constexpr int ABYTES = RT * 4 * H2_RG;       // A bytes per stage
     constexpr int STAGE = ABYTES + H2_W;
     constexpr int NST = RT == 1 ? H2_NST : 4;
@@ -303,6 +327,22 @@ __device__ __forceinline__ bool h2_phase(const H2Args& a, char* smem, int tid, i
     const int KT = h2_ksteps(K, NP), G = K / BN;   // stages per pass
     const int T = NPASS * KT;                    // stages: stage u carries W of pass u % NPASS, and A when that pass is 0
     auto colbase = [&](int pass) -> int { return NPASS == 3 ? pass * Dq + n0 : n0 + pass * BN; };
+    // PF (see H2Pf): where this phase's ring starts, whether its first W stages are already there, and whether it prefetches for
+    // the next phase -- not where its own epilogue takes the ring region (the attention through the q | k | v tile in LDS)
+    unsigned ring0 = 0;
+    bool pre = false, pf_on = false;
+    const char* pf_nw = nullptr;
+    unsigned pf_ps = 0;
+    int pf_np = 1;
+    if constexpr (PF) {
+        ring0 = pf->base;
+        pre = pf->pre != 0;
+        pf_nw = pf->nw;
+        pf_ps = pf->pstride;
+        pf_np = pf->npass;
+        pf_on = pf_nw != nullptr && !(H2_ABL & 64);
+        if (EPI == H2_EPI_ATT && !h2_att_in_registers(a.att_ntok, a.att_hd, a.rpt)) pf_on = false;
+    }
     const unsigned long long t_entry = (H2_DBG && a.dbg) ? __builtin_amdgcn_s_memtime() : 0;
 
     const int row_l = rg * 16 + li;
@@ -341,7 +381,7 @@ __device__ __forceinline__ bool h2_phase(const H2Args& a, char* smem, int tid, i
     asm volatile("" : "+v"(voW));
     const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
     int iw_t = 0, iw_g = 0, ia_t = 0, ia_kt = 0;
-    unsigned iw_slot = 0, ia_slot = 0;
+    unsigned iw_slot = ring0, ia_slot = ring0;
     const char* is_w[NPASS];
 #pragma unroll
     for (int g = 0; g < NPASS; ++g) is_w[g] = a.W2 + (size_t)(colbase(g) / BN) * KT * H2_W;
@@ -412,12 +452,13 @@ __device__ __forceinline__ bool h2_phase(const H2Args& a, char* smem, int tid, i
         }
         ++ia_kt;
     };
+    // (`pre`: the pieces are already in the ring, requested by the previous phase -- only the bookkeeping advances)
     auto issue_w = [&]() {
         const unsigned keep = dma_m0_save();
 #pragma unroll
         for (int g = 0; g < NPASS; ++g)
             if (g == iw_g) {
-                w_pieces(is_w[g], lds0 + iw_slot + (unsigned)(ABYTES + w_first * 1024));
+                if (!pre) w_pieces(is_w[g], lds0 + iw_slot + (unsigned)(ABYTES + w_first * 1024));
                 adv_w(g);
             }
         if (++iw_g == NPASS) iw_g = 0;
@@ -547,7 +588,11 @@ __device__ __forceinline__ bool h2_phase(const H2Args& a, char* smem, int tid, i
         }
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
-        if (*reinterpret_cast<volatile unsigned*>(smem + H2_FAIL)) {
+        unsigned lost = *reinterpret_cast<volatile unsigned*>(smem + H2_FAIL);
+        // PF: a scalar branch -- behind a per-lane one the ring position this phase hands to the next would count as a per-lane
+        // value where the two paths meet again, and it has to stay in a scalar register
+        if constexpr (PF) lost = (unsigned)__builtin_amdgcn_readfirstlane((int)lost);
+        if (lost) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             return false;
         }
@@ -587,6 +632,8 @@ __device__ __forceinline__ bool h2_phase(const H2Args& a, char* smem, int tid, i
     constexpr unsigned ST_LDS = DW ? 72u * 1024u /* above the A operand: the launcher keeps 2 KiB x k-tiles below it */ : (RT == 2 ? NST * STAGE : STAGE);           // + 1 KiB per wave, + 8 KiB per row tile
     constexpr bool ST_DMA = NPASS >= 2 || RT == 2;
     static_assert(RT == 1 || ST_LDS + 16384 <= H2_VEC, "statistics rows overlap the epilogue vectors");
+    // PF: "slot 1" is the slot of this phase's stage 1, one behind the rotated ring base (it holds the stages 1, 7, 13, ...: pass 1)
+    const unsigned st_lds = PF ? (ring0 + STAGE == NST * STAGE ? 0u : ring0 + (unsigned)STAGE) : ST_LDS;
     float4 st_raw[4];
     if (LNF) {
         const int ns = K / BN;
@@ -606,10 +653,10 @@ __device__ __forceinline__ bool h2_phase(const H2Args& a, char* smem, int tid, i
                     unsigned keep;
                     if (CHAIN)
                         asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off sc1\n\ts_mov_b32 m0, %0"
-                                     : "=&s"(keep) : "v"(g), "s"(lds0 + ST_LDS + (unsigned)(wave * 1024 + rt * 8192)) : "memory");
+                                     : "=&s"(keep) : "v"(g), "s"(lds0 + st_lds + (unsigned)(wave * 1024 + rt * 8192)) : "memory");
                     else
                         asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                                     : "=&s"(keep) : "v"(g), "s"(lds0 + ST_LDS + (unsigned)(wave * 1024 + rt * 8192)) : "memory");
+                                     : "=&s"(keep) : "v"(g), "s"(lds0 + st_lds + (unsigned)(wave * 1024 + rt * 8192)) : "memory");
                 }
             }
         } else {
@@ -731,7 +778,13 @@ __device__ __forceinline__ bool h2_phase(const H2Args& a, char* smem, int tid, i
     unsigned long long t_land = 0;
     {   // stage 0 (P2: the stages 0, 1, 2) landed; later ones may stay in flight: of the stages 1 .. 5, 5 / 2 / 1 carry A for
         // NPASS 1 / 2 / 3, of the stages 3, 4 (P2) 2 / 1 / 1
-        if constexpr (DW) {
+        if (PF && pre) {
+            // entered prefetched: the W pieces landed before the previous phase ended (its store drain), and this phase has
+            // requested no W yet -- the queue holds the epilogue vectors, A(0), the statistics rows and the A pieces of the later
+            // A stages, in that order.  The waves 0..3 may keep those of the stages 3, 4 in flight; the others wait for all.
+            if constexpr (HAS_A) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(APW * (NPASS == 1 ? 2 : 1)) : "memory");
+            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        } else if constexpr (DW) {
             // the A operand and the statistics rows landed (DMA); the W fragments of the first PD stages are ordinary loads the
             // compiler counts itself: the NTW * 2 * PD of them were requested BEFORE the DMA pieces, so they have landed too
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -751,7 +804,7 @@ __device__ __forceinline__ bool h2_phase(const H2Args& a, char* smem, int tid, i
 #pragma unroll
                 for (int rt = 0; rt < RT; ++rt) {
                     if constexpr (ST_DMA) {
-                        const float* sl = reinterpret_cast<const float*>(smem + ST_LDS + wave * 1024 + rt * 8192) + li * ns * 2;
+                        const float* sl = reinterpret_cast<const float*>(smem + st_lds + wave * 1024 + rt * 8192) + li * ns * 2;
 #pragma unroll
                         for (int i = 0; i < 4; ++i) st_raw[i] = (2 * i < ns) ? ld4(sl + 4 * i) : float4{0.f, 0.f, 0.f, 0.f};
                     }
@@ -787,9 +840,9 @@ __device__ __forceinline__ bool h2_phase(const H2Args& a, char* smem, int tid, i
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         if constexpr (ACT && !DW) {
-            read_a(0, A0);
+            read_a(ring0, A0);
             if (RAWX) finish_a(A0);
-            read_b(0, B0);
+            read_b(ring0, B0);
         }
         if constexpr (DW && RAWX) {
             // the raw rows become the hi | lo fragments IN PLACE (a lane's eight values are its own 16 + 16 bytes), one k-tile per
@@ -809,7 +862,7 @@ __device__ __forceinline__ bool h2_phase(const H2Args& a, char* smem, int tid, i
     }
     const unsigned long long t_loop = (H2_DBG && a.dbg) ? __builtin_amdgcn_s_memtime() : 0;
     unsigned long long t_vm = 0, t_bar = 0, t_mm = 0;      // bench-only sums: counted DMA wait, lgkm + barrier, the MFMA rows of a stage
-    unsigned slot_c = 0;
+    unsigned slot_c = ring0;
     // one stage: publish the landed stages (which frees a slot for the DMA of stage t + DIST), then the MFMAs of stage t and the
     // fragment reads of stage t+1.  REM = 0: a stage of the steady state (t + NST < T); REM > 0: a stage of the tail with REM
     // stages left including this one -- a compile-time number, so that the counted waits, the last refills and the end of the
@@ -852,7 +905,12 @@ __device__ __forceinline__ bool h2_phase(const H2Args& a, char* smem, int tid, i
                 constexpr int per = HAS_A ? WC + (NPASS == 1 ? APW : 0) : WC;
                 constexpr int allow = ahead > 0 ? ahead * per : 0;
                 static_assert(allow < 64, "vmcnt is 6 bits");
-                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(allow) : "memory");
+                // PF: the earlier tail stages (REM + 1 .. DIST) each put WC pieces of the next phase behind everything this
+                // phase requested: they may stay in flight as well
+                constexpr int allow_pf = allow + (PF && REM <= DIST ? (DIST - REM) * WC : 0);
+                static_assert(allow_pf < 64, "vmcnt is 6 bits");
+                if (PF && REM < DIST && pf_on) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(allow_pf) : "memory");
+                else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(allow) : "memory");
             }
             if (H2_DBG && a.dbg) { w1 = __builtin_amdgcn_s_memtime(); t_vm += w1 - w0; }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -876,6 +934,18 @@ __device__ __forceinline__ bool h2_phase(const H2Args& a, char* smem, int tid, i
             constexpr int gr = (g0 + DIST) % NPASS;
             if (RF && !(H2_ABL & 2))
                 refill_fast(std::integral_constant<int, gr>{}, std::integral_constant<bool, gr == 0>{}, P2 ? slot_p : slot_c);
+            if constexpr (PF && !FAST && REM <= DIST) {
+                // nothing of this phase is left to request: the W pieces of the next phase's stage j instead, into the slot a
+                // stage t + DIST of this phase would take (pass j mod npass, k step j / npass of the next W stream)
+                if (pf_on) {
+                    constexpr int j = DIST - REM;
+                    const unsigned g = pf_np == 1 ? 0u : (pf_np == 2 ? (unsigned)(j & 1) : (unsigned)(j % 3));
+                    const unsigned kt = pf_np == 1 ? (unsigned)j : (pf_np == 2 ? (unsigned)(j >> 1) : (unsigned)(j / 3));
+                    const unsigned keep = dma_m0_save();
+                    w_pieces(pf_nw + (size_t)g * pf_ps + (size_t)kt * H2_W, lds0 + slot_p + (unsigned)(ABYTES + w_first * 1024));
+                    dma_m0_restore(keep);
+                }
+            }
             if (REM == 4 && ACT) epilogue_operands();
         };
         // The two waves of a SIMD run out of phase: the waves 0..3 multiply first and load afterwards, the waves 4..7 the other
@@ -1048,6 +1118,10 @@ __device__ __forceinline__ bool h2_phase(const H2Args& a, char* smem, int tid, i
     // T - t is in [NST, NST + U - 1] and congruent to T, i.e. to 0 or NPASS, modulo U: two possible tail lengths
     constexpr int TAIL_A = (NST + U - 1) / U * U;
     constexpr int TAIL_B = (NST - NPASS + U - 1) / U * U + NPASS;
+    // PF: the counted waits of a stage that still requests count W pieces of the stages t + 2 .. t + DIST - 1 as this phase's
+    // own.  A phase entered prefetched requested none for its stages < DIST, so its tail must not start before stage DIST - 2
+    static_assert(!PF || (TAIL_A > TAIL_B ? TAIL_A : TAIL_B) + DIST - 2 <= H2_PF_MIN_T,
+                  "H2_PF_MIN_T admits a prefetched phase whose tail would under-wait");
     if (T - t == TAIL_A) tail(tail, std::integral_constant<int, TAIL_A>{}, std::integral_constant<int, 0>{});
     else tail(tail, std::integral_constant<int, TAIL_B>{}, std::integral_constant<int, 0>{});
     }
@@ -1174,6 +1248,9 @@ __device__ __forceinline__ bool h2_phase(const H2Args& a, char* smem, int tid, i
                 s1[r] = xor16_add(s1[r]); s1[r] = xor32_add(s1[r]);
             }
             float* xs = reinterpret_cast<float*>(smem) + rt * (2 * BM * 2 * NTK);     // [row tile][2 halves][64 rows][2 heads][NTK]
+            // PF: a prefetch of the next phase's W is in flight beside this exchange.  It writes W regions only, and the exchange
+            // stays inside the A region of physical slot 0 whatever stage the rotated ring put there
+            static_assert(!PF || RT * 2 * BM * 2 * NTK * (int)sizeof(float) <= ABYTES, "exchange buffer beyond the A region of slot 0");
             const int half = slot0 ? 1 : 0;
             __syncthreads();                                    // every wave is done reading the last stage
             if (kq == 0) {
@@ -1258,6 +1335,7 @@ __device__ __forceinline__ bool h2_phase(const H2Args& a, char* smem, int tid, i
                 s1[j] = xor16_add(s1[j]); s1[j] = xor32_add(s1[j]);
             }
             float* xs = reinterpret_cast<float*>(smem) + rt * (2 * BM * 8);     // [row tile][2 halves][64 rows][8]
+            static_assert(!PF || RT * 2 * BM * 8 * (int)sizeof(float) <= ABYTES, "exchange buffer beyond the A region of slot 0 (PF: W prefetch in flight)");
             const int half = slot0 ? 1 : 0;
             __syncthreads();                                    // every wave is done reading the last stage
             if (kq == 0) {
@@ -1394,6 +1472,8 @@ __device__ __forceinline__ bool h2_phase(const H2Args& a, char* smem, int tid, i
                 // LayerNorm partials {mean, M2} of the 136-column slice of each row: two exchanges through LDS
                 constexpr int XR = RT * 64;
                 float* xch = reinterpret_cast<float*>(smem);       // [2 phases][2 halves][RT x 64 rows]
+                // PF: inside the A region of physical slot 0 -- the W prefetch in flight writes W regions only
+                static_assert(!PF || 4 * XR * (int)sizeof(float) <= ABYTES, "exchange buffer beyond the A region of slot 0");
                 const int half = slot0 ? 1 : 0;
                 float sum[RT];
 #pragma unroll
@@ -1453,6 +1533,12 @@ __device__ __forceinline__ bool h2_phase(const H2Args& a, char* smem, int tid, i
             o[0] = t_entry; o[1] = t_loop; o[2] = t_epi; o[3] = t_st; o[4] = t_end; o[5] = t_vm; o[6] = t_bar; o[7] = t_mm;
             if (H2_DBG == 2) { o[5] = t_chain; o[6] = t_land; }      // prologue split: hand-off wait | first operands landed
         }
+    }
+    if constexpr (PF) {
+        // the ring position behind the last stage is where the prefetched stage 0 of the next phase went; a phase that did not
+        // prefetch hands over an empty ring, and the next one runs the whole prologue from slot 0
+        pf->base = pf_on ? slot_c : 0u;
+        pf->pre = pf_on ? 1 : 0;
     }
     return true;
 }
@@ -1556,6 +1642,14 @@ __device__ __forceinline__ int h2_team_on_one_xcd(const H2StackArgs& s, int team
     return (s.plain_ok && m != 0u && (m & (m - 1u)) == 0u) ? 1 : 0;
 }
 
+// a phase of h2_stack_kernel: the whole-tile chain form with the cross-phase W prefetch
+template <int EPI, bool LNF, int NPASS, int NTW, int WC, int NP>
+__device__ __forceinline__ bool h2_phase_pf(const H2Args& a, char* smem, int tid, int wave, int slot0, int tm, int tn,
+                                            unsigned* chain, unsigned chain_need, H2Pf& pf) {
+    return h2_phase<EPI, LNF, NPASS, NTW, true, WC, 1, NP, true, false, true>(a, smem, tid, wave, slot0, tm, tn, chain, chain_need,
+                                                                              true, 0, 4, &pf);
+}
+
 template <int NP>
 __global__ __launch_bounds__(512, 2) void h2_stack_kernel(const H2StackArgs s) {
     extern __shared__ __attribute__((aligned(1024))) char smem[];
@@ -1573,6 +1667,7 @@ __global__ __launch_bounds__(512, 2) void h2_stack_kernel(const H2StackArgs s) {
     h2_publish_xcd(s, team, tid);
     int plain = 0, seen = 0;       // plain hand-off stores once the team is known to sit on one XCD (h2_publish_xcd)
     __syncthreads();
+    H2Pf pf{0u, 0, nullptr, 0u, 1};      // cross-phase W prefetch: the first phase of the launch fills its own ring
     for (int tile0 = team; tile0 < s.n_tiles; tile0 += s.n_teams) {
         unsigned need = 0;
         for (int ph = 0; ph < s.n_phases; ++ph, need += G) {
@@ -1591,27 +1686,45 @@ __global__ __launch_bounds__(512, 2) void h2_stack_kernel(const H2StackArgs s) {
             const char* const* w = s.w[ph >> 2];
             bool ok = true;
             if (s.inject > 0 && ph == s.inject && tile == 0 && tnp == 0) return;     // fault injection (test hook)
+            // the W stream the phase behind this one starts with (H2Pf): the next phase of this tile, or the first phase of the
+            // team's next tile; nothing behind the last phase of the launch
+            {
+                int nph = ph + 1;
+                if (nph == s.n_phases) nph = tile0 + s.n_teams < s.n_tiles ? 0 : -1;
+                pf.nw = nullptr;
+                if (nph >= 0) {
+                    const int kind = nph & 3;
+                    const int npass = kind == 0 ? 3 : (kind == 2 ? 2 : 1);
+                    const int ktn = h2_ksteps(kind == 3 ? 2 * D : D, NP);
+                    if (npass * ktn >= H2_PF_MIN_T) {
+                        // column group of pass g: g G + tn (qkv), 2 tn + g (fc1), tn (proj, fc2) -- h2_phase's colbase / BN
+                        pf.nw = s.w[nph >> 2][kind] + (size_t)(npass == 3 ? tnp : npass * tnp) * ktn * H2_W;
+                        pf.pstride = (unsigned)((npass == 3 ? G : 1) * ktn * H2_W);
+                        pf.npass = npass;
+                    }
+                }
+            }
             switch (ph & 3) {
                 case 0: {   // x = x + proj(attn(qkv(norm1(x))))   (Block.forward :84-90)
                     H2Args a = h2_args_qkv<NP>(s, w[0], D, G, plain);
-                    if (wv < 4) ok = h2_phase<H2_EPI_ATT, true, 3, H2_T0, true, H2_WC0, 1, NP>(a, smem, tidp, wv, 0, tile, tnp, ctr, need);
-                    else if (wv < 6) ok = h2_phase<H2_EPI_ATT, true, 3, NT - H2_T0, true, H2_WC1, 1, NP>(a, smem, tidp, wv, H2_T0, tile, tnp, ctr, need);
-                    else ok = h2_phase<H2_EPI_ATT, true, 3, NT - H2_T0, true, H2_WC2, 1, NP>(a, smem, tidp, wv, H2_T0, tile, tnp, ctr, need);
+                    if (wv < 4) ok = h2_phase_pf<H2_EPI_ATT, true, 3, H2_T0, H2_WC0, NP>(a, smem, tidp, wv, 0, tile, tnp, ctr, need, pf);
+                    else if (wv < 6) ok = h2_phase_pf<H2_EPI_ATT, true, 3, NT - H2_T0, H2_WC1, NP>(a, smem, tidp, wv, H2_T0, tile, tnp, ctr, need, pf);
+                    else ok = h2_phase_pf<H2_EPI_ATT, true, 3, NT - H2_T0, H2_WC2, NP>(a, smem, tidp, wv, H2_T0, tile, tnp, ctr, need, pf);
                     break;
                 }
                 case 2: {   // x = x + fc2(gelu(fc1(norm2(x))))    (Block.forward :91, Mlp.forward :31-37)
                     H2Args a = h2_args_fc1<NP>(s, w[2], D, G, plain);
-                    if (wv < 4) ok = h2_phase<H2_EPI_GELU, true, 2, H2_T0, true, H2_WC0, 1, NP>(a, smem, tidp, wv, 0, tile, tnp, ctr, need);
-                    else if (wv < 6) ok = h2_phase<H2_EPI_GELU, true, 2, NT - H2_T0, true, H2_WC1, 1, NP>(a, smem, tidp, wv, H2_T0, tile, tnp, ctr, need);
-                    else ok = h2_phase<H2_EPI_GELU, true, 2, NT - H2_T0, true, H2_WC2, 1, NP>(a, smem, tidp, wv, H2_T0, tile, tnp, ctr, need);
+                    if (wv < 4) ok = h2_phase_pf<H2_EPI_GELU, true, 2, H2_T0, H2_WC0, NP>(a, smem, tidp, wv, 0, tile, tnp, ctr, need, pf);
+                    else if (wv < 6) ok = h2_phase_pf<H2_EPI_GELU, true, 2, NT - H2_T0, H2_WC1, NP>(a, smem, tidp, wv, H2_T0, tile, tnp, ctr, need, pf);
+                    else ok = h2_phase_pf<H2_EPI_GELU, true, 2, NT - H2_T0, H2_WC2, NP>(a, smem, tidp, wv, H2_T0, tile, tnp, ctr, need, pf);
                     break;
                 }
                 default: {
                     const bool fc2 = (ph & 3) == 3;
                     H2Args a = h2_args_res<NP>(s, fc2 ? w[3] : w[1], fc2, D, G, plain);
-                    if (wv < 4) ok = h2_phase<H2_EPI_RES, false, 1, H2_T0, true, H2_WC0, 1, NP>(a, smem, tidp, wv, 0, tile, tnp, ctr, need);
-                    else if (wv < 6) ok = h2_phase<H2_EPI_RES, false, 1, NT - H2_T0, true, H2_WC1, 1, NP>(a, smem, tidp, wv, H2_T0, tile, tnp, ctr, need);
-                    else ok = h2_phase<H2_EPI_RES, false, 1, NT - H2_T0, true, H2_WC2, 1, NP>(a, smem, tidp, wv, H2_T0, tile, tnp, ctr, need);
+                    if (wv < 4) ok = h2_phase_pf<H2_EPI_RES, false, 1, H2_T0, H2_WC0, NP>(a, smem, tidp, wv, 0, tile, tnp, ctr, need, pf);
+                    else if (wv < 6) ok = h2_phase_pf<H2_EPI_RES, false, 1, NT - H2_T0, H2_WC1, NP>(a, smem, tidp, wv, H2_T0, tile, tnp, ctr, need, pf);
+                    else ok = h2_phase_pf<H2_EPI_RES, false, 1, NT - H2_T0, H2_WC2, NP>(a, smem, tidp, wv, H2_T0, tile, tnp, ctr, need, pf);
                     break;
                 }
             }
