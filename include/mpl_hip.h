@@ -30,6 +30,7 @@
  *   mpl_triangulate_robust lib/multiviews/triangulate.py:88-112 (view selection by confidence) + pair consensus
  *   mpl_procrustes_align   lib/utils/pose_utils.py:61-143 (PoseUtils.procrustes, one numpy SVD per pose)
  *   mpl_synthesize_views   lib/dataset/multiview_amass_h36m_mpl.py:317-342 + joints_dataset_mpl.py:588-774 (synthetic detections)
+ *   mpl_decode_heatmaps    lib/core/inference.py:22-81 (get_max_preds, get_final_preds) + lib/utils/transforms.py:51-94
  */
 #ifndef MPL_HIP_H_
 #define MPL_HIP_H_
@@ -363,6 +364,45 @@ int mpl_linear(const float *xa, int Ka, const float *xb, int Kb, int M, const fl
 int mpl_prepare_inputs(const float *joints_px, const float *conf, const double *cams_dev, int batch, int views,
                        int joints, float img_w, float img_h, int normalize_inputs, int normalize_cameras,
                        float *const *poses, float *const *rays, float *const *centers, void *stream);
+
+/* ---- detector heatmaps -> pixel detections (-> model inputs), csrc/heatmaps.hip: the step in front of mpl_prepare_inputs, in
+ * place of lib/core/inference.py:22-81 (get_max_preds on an np.ndarray, then get_final_preds: a Python double loop over (sample,
+ * joint) and one cv2.getAffineTransform per sample, lib/utils/transforms.py:51-94), which would pull every heatmap to the host.
+ * One launch; per heatmap (b, v, j), in this order:
+ * a. peak (:34-49): idx = the first index of the maximum of the H*W values in row-major order, maxval = that value; NaN counts as
+ * the maximum and the first NaN wins (np.argmax / np.amax); -0.0 and 0.0 tie.  x = idx % W, y = idx / W, both times (maxval > 0):
+ * a map with no positive value gives (0, 0) and keeps its non-positive or NaN maxval.
+ * b. post_process != 0 (TEST.POST_PROCESS, :63-72): where 1 < x < W-1 and 1 < y < H-1 (the reference's own strict bounds),
+ * x += 0.25 * sign(hm[y][x+1] - hm[y][x-1]), y += 0.25 * sign(hm[y+1][x] - hm[y-1][x]); the sign is taken by comparison (exact
+ * for every dtype), a NaN neighbour gives a NaN coordinate.  -> coords, in heatmap cells.
+ * c. back to the image (transform_preds with rot = 0): k = scale[b,v,0] * 200 / W, pixel = center[b,v] + (coord - (W/2, H/2)) * k,
+ * isotropic, scale[b,v,1] is not read (as in the reference); fp64 on the fp32 inputs, rounded once.  Without center / scale
+ * pixels = coords.  The one deviation: the reference rounds the three anchor points of its affine fit to float32 before it
+ * solves, the closed form does not (on the committed golden at most 3 fp32 ulps, and 20 at one pixel that is the small difference of
+ * two large terms, where the rounded anchors are the ones in error).
+ * d. pixels (B,V,J,2) and conf (B,V,J) = maxval are the joints_px / conf of mpl_prepare_inputs.  With cams_dev the same thread goes
+ * on with the arithmetic of mpl_prepare_inputs on the fp32-rounded pixel and writes poses / rays / centers: bitwise what
+ * mpl_prepare_inputs writes from pixels and conf.
+ * heatmaps: HOST array of `views` device pointers; view v holds (B,J,H,W) values of `dtype` (MPL_HM_*), sample b starting at
+ * element b * batch_stride: batch_stride = J*H*W for V separate tensors, V*J*H*W with heatmaps[v] = base + v*J*H*W for one
+ * contiguous (B,V,J,H,W) tensor -- both are read in place.  16-bit values are widened exactly: decoding a 16-bit map equals
+ * decoding its fp32 upcast bit for bit.  center, scale: device fp32 (B,V,2), both or neither.  coords: (B,V,J,2) or NULL.
+ * cams_dev / img_w / img_h / normalize_* / poses / rays / centers: as for mpl_prepare_inputs; cams_dev NULL = no model inputs (the
+ * tables are then not read).
+ * A map whose base address and byte size are multiples of 16 is read with 16-byte loads, any other element by element; a map of
+ * 64 KiB or more is shared by the four waves of a workgroup, a smaller one read by one wave.  The merge is a total order (NaN,
+ * then value, then lower index), so all of these give identical outputs, run to run and batching to batching.
+ * MPL_E_INVALID: heatmaps, one of its first `views` entries, pixels or conf NULL; a non-positive size; center without scale or the
+ * reverse; cams_dev without all three tables, with a NULL entry in one, or with img_w / img_h <= 0; an unknown dtype;
+ * batch_stride < J*H*W.  MPL_E_UNSUPPORTED: views > MPL_MAX_VIEWS, H*W > 2^20, batch*views*joints > 2^30.  All before any launch.
+ * Stream-ordered, never synchronises; like the geometry calls it neither looks at nor sets the device error word. */
+#define MPL_HM_F32 0
+#define MPL_HM_F16 1
+#define MPL_HM_BF16 2
+int mpl_decode_heatmaps(const void *const *heatmaps, int dtype, long long batch_stride, int batch, int views, int joints,
+                        int height, int width, int post_process, const float *center, const float *scale, float *pixels,
+                        float *conf, float *coords, const double *cams_dev, float img_w, float img_h, int normalize_inputs,
+                        int normalize_cameras, float *const *poses, float *const *rays, float *const *centers, void *stream);
 
 /* ---- synthesis of the multi-view model inputs from 3D poses, csrc/synth.hip: the producer in front of mpl_prepare_inputs, in
  * place of what the reference's synthetic datasets run in numpy per sample and view inside Dataset.__getitem__:

@@ -24,4 +24,7 @@ def __getattr__(name):
     if name in ("synthesize_views", "project_points"):
         from . import synth
         return getattr(synth, name)
+    if name == "decode_heatmaps":
+        from .heatmaps import decode_heatmaps
+        return decode_heatmaps
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

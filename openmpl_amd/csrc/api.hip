@@ -814,6 +814,16 @@ int mpl_prepare_inputs(const float* joints_px, const float* conf, const double* 
                                  normalize_cameras, poses, rays, centers, (hipStream_t)stream);
 }
 
+int mpl_decode_heatmaps(const void* const* heatmaps, int dtype, long long batch_stride, int batch, int views, int joints, int height,
+                        int width, int post_process, const float* center, const float* scale, float* pixels, float* conf,
+                        float* coords, const double* cams_dev, float img_w, float img_h, int normalize_inputs, int normalize_cameras,
+                        float* const* poses, float* const* rays, float* const* centers, void* stream) {
+    clear_stale_hip_error();
+    return launch_decode_heatmaps(heatmaps, dtype, batch_stride, batch, views, joints, height, width, post_process, center, scale,
+                                  pixels, conf, coords, cams_dev, img_w, img_h, normalize_inputs, normalize_cameras, poses, rays,
+                                  centers, (hipStream_t)stream);
+}
+
 int mpl_synthesize_views(const float* poses3d, const double* cams_dev, const mpl_synth_options* opt, const float* conf,
                          const float* rotation_deg, const float* translation, const float* noise, const float* missing_u, int batch,
                          int views, int joints, float* const* poses, float* const* rays, float* const* centers, float* target,

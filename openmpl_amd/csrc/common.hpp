@@ -324,6 +324,12 @@ int launch_prepare_inputs(const float* px, const float* conf, const double* cams
                           int norm_in, int norm_cam, float* const* poses, float* const* rays, float* const* centers,
                           hipStream_t s);
 
+// heatmaps.hip: detector heatmaps -> pixels, confidences and (with cameras) model inputs (mpl_decode_heatmaps)
+int launch_decode_heatmaps(const void* const* heatmaps, int dtype, long long batch_stride, int B, int V, int J, int H, int W,
+                           int post_process, const float* center, const float* scale, float* pixels, float* conf, float* coords,
+                           const double* cams_dev, float img_w, float img_h, int norm_in, int norm_cam, float* const* poses,
+                           float* const* rays, float* const* centers, hipStream_t s);
+
 // geometry.hip: triangulation of the model's rays and the epipolar consistency score (mpl_triangulate_rays, mpl_epipolar_errors,
 // mpl_triangulate_robust)
 int launch_triangulate_rays(const float* const* rays, const float* const* centers, const float* const* conf, int conf_stride, int B,

@@ -8,6 +8,7 @@
 // V x (B,J,3) rays and V x (B,1,3) centers that mpl_forward consumes (150 B/pose of raw input instead of 1680 B).
 // Arithmetic is fp64 and rounded once, like the reference's float64 numpy followed by .float().
 #include "common.hpp"
+#include "inputs.hpp"
 
 namespace mpl {
 
@@ -28,33 +29,9 @@ __global__ __launch_bounds__(256) void prepare_inputs_kernel(const PrepParams p)
     const int total = p.B * p.V * p.J;
     if (idx >= total) return;
     const int j = idx % p.J, v = (idx / p.J) % p.V, b = idx / (p.J * p.V);
-    const double* c = p.cams + v * 16;
-    double fx = c[0], fy = c[1], cx = c[2], cy = c[3];
-    double x = p.px[(size_t)idx * 2], y = p.px[(size_t)idx * 2 + 1];
-    if (p.norm_in) {
-        x = (x / p.w) * 2.0 - 1.0;
-        y = (y / p.w) * 2.0 - p.h / p.w;
-        if (p.norm_cam) {
-            cx = (cx / p.w) * 2.0 - 1.0;
-            cy = (cy / p.w) * 2.0 - p.h / p.w;
-            fx = fx / p.w * 2.0;
-            fy = fy / p.w * 2.0;
-        }
-    }
-    const double u0 = (x - cx) / fx, u1 = (y - cy) / fy, u2 = 1.0;
     const size_t o = ((size_t)b * p.J + j) * 3;
-    float* po = p.poses[v] + o;
-    po[0] = (float)x;
-    po[1] = (float)y;
-    po[2] = p.conf ? p.conf[idx] : 1.0f;
-    float* ro = p.rays[v] + o;
-#pragma unroll
-    for (int d = 0; d < 3; ++d) ro[d] = (float)(u0 * c[4 + d] + u1 * c[7 + d] + u2 * c[10 + d] + c[13 + d]);   // R^T u + t
-    if (j == 0) {
-        float* co = p.centers[v] + (size_t)b * 3;
-#pragma unroll
-        for (int d = 0; d < 3; ++d) co[d] = (float)c[13 + d];
-    }
+    prepare_point(p.cams + v * 16, p.px[(size_t)idx * 2], p.px[(size_t)idx * 2 + 1], p.conf ? p.conf[idx] : 1.0f, p.w, p.h, p.norm_in,
+                  p.norm_cam, p.poses[v] + o, p.rays[v] + o, j == 0 ? p.centers[v] + (size_t)b * 3 : nullptr);
 }
 
 int launch_prepare_inputs(const float* px, const float* conf, const double* cams_dev, int B, int V, int J, float w, float h,
