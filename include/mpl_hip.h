@@ -31,6 +31,7 @@
  *   mpl_procrustes_align   lib/utils/pose_utils.py:61-143 (PoseUtils.procrustes, one numpy SVD per pose)
  *   mpl_synthesize_views   lib/dataset/multiview_amass_h36m_mpl.py:317-342 + joints_dataset_mpl.py:588-774 (synthetic detections)
  *   mpl_decode_heatmaps    lib/core/inference.py:22-81 (get_max_preds, get_final_preds) + lib/utils/transforms.py:51-94
+ *   mpl_rpsm               lib/multiviews/pictorial.py:18-247 (rpsm, recursive_infer, infer, compute_unary_term, compute_grid)
  */
 #ifndef MPL_HIP_H_
 #define MPL_HIP_H_
@@ -403,6 +404,57 @@ int mpl_decode_heatmaps(const void *const *heatmaps, int dtype, long long batch_
                         int height, int width, int post_process, const float *center, const float *scale, float *pixels,
                         float *conf, float *coords, const double *cams_dev, float img_w, float img_h, int normalize_inputs,
                         int normalize_cameras, float *const *poses, float *const *rays, float *const *centers, void *stream);
+
+/* ---- recursive pictorial structure model, csrc/rpsm.hip: a 3D pose from the WHOLE heatmaps of all views, in place of
+ * lib/multiviews/pictorial.py (numpy, fp64; one pose at a time, a dense nbins x nbins product per edge: 11 s per pose at 16^3 bins).
+ * The numpy file is the reference, not pictorial_cuda.py: no [h-1, w-1] mix-up and no soft grid_sample border.  fp64 arithmetic on
+ * the fp32 / 16-bit inputs; 2 + (number of tree levels that have children) launches, whatever batch and recur_depth.
+ * Grid (compute_grid :106-117): l = linspace(-size/2, size/2, n) (i * step + start, the last point the stop), meshgrid in its default
+ * xy indexing: bin (iy*n + ix)*n + iz is (l[ix] + cx, l[iy] + cy, l[iz] + cz) -- y slowest, z fastest; ties go to the first index.
+ * Unary (compute_unary_term :144-188): per joint and bin 0.0 plus, view after view, the view's map of the joint sampled at the
+ * projection of the bin: x_cam = R (X - t) (the layout of mpl_prepare_inputs), y = x_cam.xy / z, r2 = |y|^2,
+ * y' = y (1 + k1 r2 + k2 r2^2 + k3 r2^3 + 2 p1 y.y + 2 p2 y.x) + (p2, p1) r2 (cameras.py:39-45; dist_dev (V,5) k1 k2 k3 p1 p2, NULL =
+ * zeros, which give the pinhole bit for bit), px = f y' + c; the crop with rot = 0 in closed form,
+ * u = ((px - center) * img_w / (200 * scale_x) + (img_w, img_h) / 2) * (W, H) / (img_w, img_h) (isotropic, scale_y is not read; the
+ * inverse of mpl_decode_heatmaps step c; within 7e-15 of the reference's affine solve); then bilinear interpolation of the map at
+ * (u_x, u_y) in cells, 0 outside [0, W-1] x [0, H-1] with the borders inside (RegularGridInterpolator(bounds_error=False,
+ * fill_value=0); the reference's call only works for square maps, non-square ones get the obvious meaning).
+ * Deviation 1 (as in mpl_synthesize_views): a point with z_cam <= 1e-9 contributes 0 from that view.
+ * Max-product (infer :18-84): children before parents; a leaf's energy is its unary; for child c of a node and parent bin i the
+ * candidates are all child bins j: energy_c[j] where | |g_parent[i] - g_child[j]| - limb[c] | <= tolerance, else 0.0; the first index
+ * of the maximum is the back-pointer; the node's energy is its unary times the maxima of its children in ascending child order;
+ * the root's first argmax, then down the back-pointers.  NaN counts as the maximum and the first NaN wins (np.argmax).
+ * Deviation 2: a disallowed pair is 0.0 even where the child's energy is NaN (the reference multiplies 0 * NaN).
+ * In the first round the grid is shared, so the norm depends on m = dix^2 + diy^2 + diz^2 only: the decision is taken as
+ * | sqrt(m) * (grid_size / (n-1)) - limb | <= tolerance, which differs from the reference's norm of rounded coordinates only within
+ * rounding of the boundary.
+ * Recursion (rpsm :233-247): cur = grid_size / first_nbins; recur_depth times: a grid of recur_nbins^3 bins of extent cur about every
+ * joint's current point, unary on the joint's own grid, pairwise by the norm between the two joints' grids, the same inference,
+ * cur /= recur_nbins.  recur_depth = 0 returns the first round.
+ * heatmaps / dtype / batch_stride: as for mpl_decode_heatmaps, read in place.  center, scale: device fp32 (B,V,2).  cams_dev: device
+ * (V,16) doubles.  root_center: device fp32 (B,3).  limb: device fp32, row b at limb + b * limb_stride (limb_stride 0: one row for
+ * every pose), indexed by the child joint, the root's entry not read.  parents: HOST array of `joints` ints, -1 for the one root.
+ * workspace: mpl_rpsm_workspace_bytes(batch, joints, first_nbins) device bytes (fp64 energies per joint and bin, a 16-bit
+ * back-pointer per edge and parent bin: 0.7 MB per pose at 17 joints and 16^3).
+ * Outputs: poses (B,J,3) fp32, the fp64 grid point rounded once; bins (B, 1 + recur_depth, J) int32, the chosen bin of every round;
+ * energy (B) doubles, the root's maximum of the first round.
+ * stages: MPL_RPSM_ALL, or for measurements a subset of MPL_RPSM_UNARY | MPL_RPSM_LEVELS | MPL_RPSM_FINAL: only those launches
+ * are issued, on the workspace as the call before left it.
+ * Envelope: first_nbins 2..16, recur_nbins 2..4, recur_depth 0..16, joints <= 64, views <= MPL_MAX_VIEWS, H, W >= 2,
+ * H*W <= 2^20, batch <= 2^20: MPL_E_UNSUPPORTED outside.  MPL_E_INVALID: a NULL pointer (dist_dev excepted), a non-positive
+ * size, an unknown dtype, img_w / img_h / grid_size <= 0, tolerance < 0, 0 < limb_stride < joints, batch_stride < J*H*W, parents
+ * that are not one tree with exactly one root, stages outside 1..7.  MPL_E_WORKSPACE: workspace NULL or too small.  All before any
+ * launch.  Stream-ordered, never synchronises; neither looks at nor sets the device error word. */
+#define MPL_RPSM_UNARY 1
+#define MPL_RPSM_LEVELS 2
+#define MPL_RPSM_FINAL 4
+#define MPL_RPSM_ALL 7
+size_t mpl_rpsm_workspace_bytes(int batch, int joints, int first_nbins); /* 0 outside the envelope */
+int mpl_rpsm(const void *const *heatmaps, int dtype, long long batch_stride, int batch, int views, int joints, int height, int width,
+             const float *center, const float *scale, const double *cams_dev, const double *dist_dev, double img_w, double img_h,
+             const float *root_center, const float *limb, long long limb_stride, const int *parents, int first_nbins,
+             int recur_nbins, int recur_depth, double grid_size, double tolerance, void *workspace, size_t workspace_bytes,
+             float *poses, int32_t *bins, double *energy, int stages, void *stream);
 
 /* ---- synthesis of the multi-view model inputs from 3D poses, csrc/synth.hip: the producer in front of mpl_prepare_inputs, in
  * place of what the reference's synthetic datasets run in numpy per sample and view inside Dataset.__getitem__:

@@ -27,4 +27,8 @@ def __getattr__(name):
     if name == "decode_heatmaps":
         from .heatmaps import decode_heatmaps
         return decode_heatmaps
+    if name == "rpsm":
+        # the module is callable (openmpl_amd.rpsm(...)); importing it binds this attribute for good
+        import importlib
+        return importlib.import_module(".rpsm", __name__)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -824,6 +824,19 @@ int mpl_decode_heatmaps(const void* const* heatmaps, int dtype, long long batch_
                                   centers, (hipStream_t)stream);
 }
 
+size_t mpl_rpsm_workspace_bytes(int batch, int joints, int first_nbins) { return rpsm_workspace_bytes(batch, joints, first_nbins); }
+
+int mpl_rpsm(const void* const* heatmaps, int dtype, long long batch_stride, int batch, int views, int joints, int height, int width,
+             const float* center, const float* scale, const double* cams_dev, const double* dist_dev, double img_w, double img_h,
+             const float* root_center, const float* limb, long long limb_stride, const int* parents, int first_nbins, int recur_nbins,
+             int recur_depth, double grid_size, double tolerance, void* workspace, size_t workspace_bytes, float* poses, int32_t* bins,
+             double* energy, int stages, void* stream) {
+    clear_stale_hip_error();
+    return launch_rpsm(heatmaps, dtype, batch_stride, batch, views, joints, height, width, center, scale, cams_dev, dist_dev, img_w,
+                       img_h, root_center, limb, limb_stride, parents, first_nbins, recur_nbins, recur_depth, grid_size, tolerance,
+                       workspace, workspace_bytes, poses, bins, energy, stages, (hipStream_t)stream);
+}
+
 int mpl_synthesize_views(const float* poses3d, const double* cams_dev, const mpl_synth_options* opt, const float* conf,
                          const float* rotation_deg, const float* translation, const float* noise, const float* missing_u, int batch,
                          int views, int joints, float* const* poses, float* const* rays, float* const* centers, float* target,

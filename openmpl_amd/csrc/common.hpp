@@ -330,6 +330,14 @@ int launch_decode_heatmaps(const void* const* heatmaps, int dtype, long long bat
                            const double* cams_dev, float img_w, float img_h, int norm_in, int norm_cam, float* const* poses,
                            float* const* rays, float* const* centers, hipStream_t s);
 
+// rpsm.hip: the recursive pictorial structure model on whole heatmaps (mpl_rpsm)
+size_t rpsm_workspace_bytes(int B, int J, int first_nbins);
+int launch_rpsm(const void* const* heatmaps, int dtype, long long batch_stride, int B, int V, int J, int H, int W, const float* center,
+                const float* scale, const double* cams_dev, const double* dist_dev, double img_w, double img_h, const float* root_center,
+                const float* limb, long long limb_stride, const int* parents, int first_nbins, int recur_nbins, int recur_depth,
+                double grid_size, double tolerance, void* workspace, size_t workspace_bytes, float* poses, int* bins, double* energy,
+                int stages, hipStream_t s);
+
 // geometry.hip: triangulation of the model's rays and the epipolar consistency score (mpl_triangulate_rays, mpl_epipolar_errors,
 // mpl_triangulate_robust)
 int launch_triangulate_rays(const float* const* rays, const float* const* centers, const float* const* conf, int conf_stride, int B,

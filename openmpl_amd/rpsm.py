@@ -1,0 +1,197 @@
+"""Recursive pictorial structure model (RPSM) on the device: a 3D pose from the whole heatmaps of all views.
+
+Reference: lib/multiviews/pictorial.py:18-247 (rpsm, recursive_infer, infer, compute_unary_term, compute_pairwise_constrain,
+compute_grid; numpy, fp64, one pose at a time) with the tree of lib/multiviews/body.py.  HIP kernels through the C ABI (mpl_rpsm,
+csrc/rpsm.hip) on the current stream: no synchronisation, no host read-back, no CPU path, and the heatmaps are read where they lie.
+
+The package attribute `openmpl_amd.rpsm` is this module, and the module is callable: openmpl_amd.rpsm(...) is rpsm(...) below.
+"""
+from __future__ import annotations
+
+import sys
+import types
+from typing import NamedTuple, Optional, Sequence, Tuple, Union
+
+import torch
+
+from . import cabi
+from .heatmaps import _DTYPES, _in_place
+
+# lib/multiviews/body.py:17-33 (HumanBody.get_skeleton) restated as parents: root, rhip, rkne, rank, lhip, lkne, lank, belly, neck,
+# nose, head, lsho, lelb, lwri, rsho, relb, rwri
+HUMAN_BODY_PARENTS = (-1, 0, 1, 2, 0, 4, 5, 0, 7, 8, 9, 8, 11, 12, 8, 14, 15)
+MAX_JOINTS = 64
+FIRST_NBINS = (2, 16)
+RECUR_NBINS = (2, 4)
+RECUR_DEPTH = (0, 16)
+
+
+class RPSMResult(NamedTuple):
+    poses: torch.Tensor        # (B,J,3) float32: the float64 grid point of the last round, rounded once
+    bins: torch.Tensor         # (B, 1 + recur_depth, J) int32: the chosen bin of every round
+    energy: torch.Tensor       # (B,) float64: the root's maximum in the first round
+
+
+def tree_levels(parents: Sequence[int]) -> int:
+    """The number of tree levels that have children (the depth of the deepest joint); ValueError unless `parents` is one tree with
+    exactly one root (-1)."""
+    parents = [int(q) for q in parents]
+    J = len(parents)
+    if sum(1 for q in parents if q == -1) != 1:
+        raise ValueError("parents must have exactly one root (-1), got %r" % (parents,))
+    deepest = 0
+    for j, q in enumerate(parents):
+        if q != -1 and not (0 <= q < J and q != j):
+            raise ValueError("parents[%d] = %d is no joint of 0..%d" % (j, q, J - 1))
+        d, k = 0, j
+        while parents[k] != -1:
+            k = parents[k]
+            d += 1
+            if d >= J:
+                raise ValueError("parents has a cycle through joint %d" % j)
+        deepest = max(deepest, d)
+    return deepest
+
+
+def launches(parents: Optional[Sequence[int]] = None) -> int:
+    """Kernel launches of one rpsm() call: the unary term, one per tree level that has children, and the launch that walks the tree
+    down and runs every recursion round -- 7 for the default body, whatever the batch and recur_depth."""
+    return 2 + tree_levels(HUMAN_BODY_PARENTS if parents is None else parents)
+
+
+def _check(heatmaps, center, scale, cams, image_size, root_center, limb_length, parents, first_nbins, recur_nbins, recur_depth,
+           grid_size, tolerance, distortion):
+    """Shapes and the envelope first (ValueError, nothing loaded), then dtypes, then devices."""
+    if isinstance(heatmaps, torch.Tensor):
+        if heatmaps.ndim != 5 or min(heatmaps.shape) < 1:
+            raise ValueError("heatmaps: expected one (B,V,J,H,W) tensor or a list of V (B,J,H,W) tensors, got shape %s" % (tuple(heatmaps.shape),))
+        B, V, J, H, W = heatmaps.shape
+        views, maps = None, [heatmaps]
+    else:
+        if not isinstance(heatmaps, (list, tuple)) or len(heatmaps) == 0 or not all(isinstance(t, torch.Tensor) for t in heatmaps):
+            raise ValueError("heatmaps must be one (B,V,J,H,W) tensor or a non-empty list of tensors, one per view")
+        views = maps = list(heatmaps)
+        V = len(views)
+        if views[0].ndim != 4 or min(views[0].shape) < 1:
+            raise ValueError("heatmaps[0]: expected shape (B,J,H,W), got %s" % (tuple(views[0].shape),))
+        B, J, H, W = views[0].shape
+        for v, t in enumerate(views):
+            if tuple(t.shape) != (B, J, H, W):
+                raise ValueError("heatmaps[%d]: expected shape %s, got %s" % (v, (B, J, H, W), tuple(t.shape)))
+    if parents is None:
+        if J != len(HUMAN_BODY_PARENTS):
+            raise ValueError("the default tree has %d joints, the heatmaps %d: pass parents" % (len(HUMAN_BODY_PARENTS), J))
+        parents = HUMAN_BODY_PARENTS
+    if isinstance(parents, torch.Tensor):
+        if parents.device.type != "cpu":
+            raise ValueError("parents is read on the host: pass a list or a CPU tensor")
+        parents = parents.tolist()
+    parents = [int(q) for q in parents]
+    if len(parents) != J:
+        raise ValueError("parents has %d entries, the heatmaps %d joints" % (len(parents), J))
+    for what, val, (lo, hi) in (("first_nbins", first_nbins, FIRST_NBINS), ("recur_nbins", recur_nbins, RECUR_NBINS),
+                                ("recur_depth", recur_depth, RECUR_DEPTH)):
+        if int(val) != val or not lo <= val <= hi:
+            raise ValueError("%s must be an integer in %d..%d, got %r" % (what, lo, hi, val))
+    if J > MAX_JOINTS or V > cabi.MPL_MAX_VIEWS or H < 2 or W < 2 or H * W > 1 << 20 or B > 1 << 20:
+        raise ValueError("at most %d joints, %d views, maps of 2x2 to 2^20 values and 2^20 poses (got %d joints, %d views, %dx%d maps, "
+                         "%d poses)" % (MAX_JOINTS, cabi.MPL_MAX_VIEWS, J, V, H, W, B))
+    levels = tree_levels(parents)
+    if not (float(grid_size) > 0 and float(tolerance) >= 0):
+        raise ValueError("grid_size must be positive and tolerance non-negative, got %r and %r" % (grid_size, tolerance))
+    if len(image_size) != 2 or not (float(image_size[0]) > 0 and float(image_size[1]) > 0):
+        raise ValueError("image_size must be a positive (w, h), got %r" % (tuple(image_size),))
+    if not isinstance(limb_length, torch.Tensor) or tuple(limb_length.shape) not in ((J,), (B, J)):
+        raise ValueError("limb_length: expected a tensor of shape %s or %s, got %s"
+                         % ((J,), (B, J), tuple(limb_length.shape) if isinstance(limb_length, torch.Tensor) else type(limb_length).__name__))
+    named = [("center", center, (B, V, 2), torch.float32), ("scale", scale, (B, V, 2), torch.float32), ("cams", cams, (V, 16), torch.float64),
+             ("root_center", root_center, (B, 3), torch.float32), ("limb_length", limb_length, tuple(limb_length.shape), torch.float32)]
+    if distortion is not None:
+        named.append(("distortion", distortion, (V, 5), torch.float64))
+    for what, t, shape, _ in named:
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape:
+            raise ValueError("%s: expected a tensor of shape %s, got %s" % (what, shape, tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__))
+    # dtypes
+    for v, t in enumerate(maps):
+        if t.dtype not in _DTYPES or t.dtype != maps[0].dtype:
+            raise ValueError("heatmaps must be float32, float16 or bfloat16, all alike (%s is %s)" % ("heatmaps" if views is None else "heatmaps[%d]" % v, t.dtype))
+    for what, t, _, want in named:
+        if t.dtype != want:
+            raise ValueError("%s must be %s (is %s)%s" % (what, want, t.dtype, " (see pack_cameras)" if what == "cams" else ""))
+    # devices
+    dev = maps[0].device
+    for what, t in [("heatmaps" if views is None else "heatmaps[%d]" % v, t) for v, t in enumerate(maps)] + [(n, t) for n, t, _, _ in named]:
+        if t.device.type != "cuda":
+            raise RuntimeError("rpsm has no CPU path: %s must live on a GPU" % what)
+        if t.device != dev:
+            raise RuntimeError("%s is on %s, the heatmaps on %s" % (what, t.device, dev))
+    return views, parents, levels, B, V, J, H, W
+
+
+def rpsm(heatmaps: Union[torch.Tensor, Sequence[torch.Tensor]], center: torch.Tensor, scale: torch.Tensor, cams: torch.Tensor,
+         image_size: Tuple[float, float], root_center: torch.Tensor, limb_length: torch.Tensor, *, parents: Optional[Sequence[int]] = None,
+         first_nbins: int = 16, recur_nbins: int = 2, recur_depth: int = 10, grid_size: float = 2000.0, tolerance: float = 150.0,
+         distortion: Optional[torch.Tensor] = None, _stages: int = cabi.RPSM_ALL, _workspace: Optional[torch.Tensor] = None) -> RPSMResult:
+    """heatmaps: what decode_heatmaps takes and reads in place -- a list of V (B,J,H,W) tensors or one (B,V,J,H,W) tensor; float32,
+    float16 or bfloat16 on a GPU (16-bit maps count as their float32 upcast, bit for bit).  center, scale (B,V,2) float32: the crop
+    boxes of the detector.  cams (V,16) float64 (pack_cameras).  image_size (w, h): the network input the crop maps to
+    (NETWORK.IMAGE_SIZE).  root_center (B,3) float32: the centre of the first grid, in the cameras' world units.  limb_length (J,) or
+    (B,J) float32, indexed by the child joint; the root's entry is not read.  parents: J ints, -1 for the one root (default: the
+    17-joint HumanBody tree).  distortion: (V,5) float64 k1, k2, k3, p1, p2 or None (pinhole; zeros give the same bits).
+
+    1. A grid of first_nbins^3 points over a box of grid_size about root_center, shared by all joints; bin (iy*n + ix)*n + iz.
+    2. Unary term per joint and bin: the sum over the views of the view's heatmap, bilinearly interpolated at the projection of the
+       bin (0 outside the map, 0 from a view the point is not in front of).
+    3. Max-product over the tree, children first: for a parent bin the best child bin among those whose distance to it is within
+       `tolerance` of the limb length (every other child bin counts 0.0; the first index wins a tie; NaN counts as the maximum).
+       The root's first maximum (`energy`) and the back-pointers give one bin per joint.
+    4. recur_depth times: a grid of recur_nbins^3 points about every joint's current point, of a first-round cell's extent and
+       recur_nbins times smaller each round; steps 2 and 3 on those grids.
+
+    Returns RPSMResult(poses (B,J,3) float32, bins (B, 1 + recur_depth, J) int32, energy (B,) float64).  poses go straight into
+    PoseEvaluator.update (scale= for the units).  Envelope: first_nbins 2..16, recur_nbins 2..4, recur_depth 0..16, at most 64 joints
+    and 32 views; anything else is a ValueError before anything is launched.  launches(parents) kernel launches: 2 + the number
+    of tree levels that have children, 7 for the default tree, whatever the batch and recur_depth.
+    (_stages, _workspace: for tools/rpsm_prof.py, which issues the stages of a call one by one on a buffer it keeps.)"""
+    views, parents, _, B, V, J, H, W = _check(heatmaps, center, scale, cams, image_size, root_center, limb_length, parents, first_nbins,
+                                              recur_nbins, recur_depth, grid_size, tolerance, distortion)
+    inner = (J, H, W)
+    if views is None:
+        hm = heatmaps if _in_place(heatmaps, inner) else heatmaps.contiguous()
+        keep = [hm]
+        ptrs = [hm.data_ptr() + v * hm.stride(1) * hm.element_size() for v in range(V)]
+    else:
+        ok = all(_in_place(t, inner) for t in views) and (B == 1 or len({t.stride(0) for t in views}) == 1)
+        keep = views if ok else [t.contiguous() for t in views]
+        ptrs = [t.data_ptr() for t in keep]
+    stride = keep[0].stride(0) if B > 1 else J * H * W
+    dev = keep[0].device
+    lib = cabi.load()
+    center, scale, cams, root_center, limb_length = (t.contiguous() for t in (center, scale, cams, root_center, limb_length))
+    if distortion is not None:
+        distortion = distortion.contiguous()
+    first_nbins, recur_nbins, recur_depth = int(first_nbins), int(recur_nbins), int(recur_depth)
+    need = lib.mpl_rpsm_workspace_bytes(B, J, first_nbins)
+    ws = _workspace if _workspace is not None else torch.empty(need, dtype=torch.uint8, device=dev)
+    poses = torch.empty((B, J, 3), dtype=torch.float32, device=dev)
+    bins = torch.empty((B, 1 + recur_depth, J), dtype=torch.int32, device=dev)
+    energy = torch.empty((B,), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.mpl_rpsm((cabi._fp * V)(*ptrs), _DTYPES[keep[0].dtype], stride, B, V, J, H, W, center.data_ptr(), scale.data_ptr(),
+                          cams.data_ptr(), None if distortion is None else distortion.data_ptr(), float(image_size[0]), float(image_size[1]),
+                          root_center.data_ptr(), limb_length.data_ptr(), J if limb_length.ndim == 2 else 0, (cabi.C.c_int * J)(*parents),
+                          first_nbins, recur_nbins, recur_depth, float(grid_size), float(tolerance), ws.data_ptr(), ws.numel(),
+                          poses.data_ptr(), bins.data_ptr(), energy.data_ptr(), int(_stages), torch.cuda.current_stream().cuda_stream)
+    cabi.check(rc, "mpl_rpsm")
+    return RPSMResult(poses, bins, energy)
+
+
+class _CallableModule(types.ModuleType):
+    """`openmpl_amd.rpsm` names both this module and its function: importing the module binds the package attribute to the module,
+    so the module itself takes the call."""
+
+    def __call__(self, *args, **kwargs):
+        return rpsm(*args, **kwargs)
+
+
+sys.modules[__name__].__class__ = _CallableModule

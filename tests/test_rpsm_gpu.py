@@ -1,0 +1,143 @@
+"""openmpl_amd.rpsm (csrc/rpsm.hip) on the device against the float64 restatement of tests/rpsm_cases.py: bins exact, poses within 1
+float32 ulp, energy within 1e-12 relative, on cases built so that no decision sits within rounding of a tie (conditions (a) and (b)
+there); against the reference-generated golden at 16^3; and in a closed loop behind project_points."""
+import numpy as np
+import pytest
+import torch
+
+from tests import rpsm_cases as rc
+
+pytestmark = pytest.mark.gpu
+
+
+def _dev(x):
+    return None if x is None else torch.from_numpy(np.array(x)).cuda()                  # a copy: the cached cases are read-only
+
+
+def _args(inp, dtype=None, as_list=False):
+    hm = _dev(inp["hm"])
+    if dtype is not None:
+        hm = hm.to(dtype)
+    if as_list:
+        hm = [hm[:, v].contiguous() for v in range(hm.shape[1])]
+    kw = dict(inp["kw"], parents=inp["parents"], distortion=_dev(inp["dist"]))
+    return (hm, _dev(inp["center"]), _dev(inp["scale"]), _dev(inp["cams"]), inp["image_size"], _dev(inp["root_center"]), _dev(inp["limb"])), kw
+
+
+def _run(inp, **over):
+    import openmpl_amd
+    args, kw = _args(inp, over.pop("dtype", None), over.pop("as_list", False))
+    kw.update(over)
+    return openmpl_amd.rpsm(*args, **kw)
+
+
+def _same(a, b):
+    return all(x.shape == y.shape and torch.equal(x.contiguous().view(torch.uint8), y.contiguous().view(torch.uint8)) for x, y in zip(a, b))
+
+
+def _check(r, ref, what):
+    bins, poses, energy = r.bins.cpu().numpy(), r.poses.cpu().numpy(), r.energy.cpu().numpy()
+    assert r.bins.dtype == torch.int32 and r.poses.dtype == torch.float32 and r.energy.dtype == torch.float64
+    wrong = int((bins != ref["bins"]).sum())
+    u = rc.ulps(poses, ref["poses"].astype(np.float32))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        rel = np.where((energy == ref["energy"]) | (np.isnan(energy) & np.isnan(ref["energy"])), 0.0, np.abs(energy - ref["energy"]) / np.abs(ref["energy"]))
+    print("%s: %d of %d bins differ, poses at most %.1f ulp, energy at most %.1e relative" % (what, wrong, bins.size, u.max(), rel.max()))
+    assert bins.shape == ref["bins"].shape and wrong == 0, what
+    assert u.max() <= 1.0, what
+    assert np.array_equal(np.isnan(energy), np.isnan(ref["energy"])) and rel.max() <= 1e-12, what
+
+
+def _launches(fn):
+    from openmpl_amd import cabi
+    torch.cuda.synchronize()
+    cabi.profile_start()
+    try:
+        res = fn()
+    finally:
+        torch.cuda.synchronize()
+        counts = cabi.profile_stop()
+    return res, sum(n for _, n in counts.values())
+
+
+@pytest.mark.parametrize("name", ["n2", "n3", "n5", "n8", "n11", "single", "chain_r3", "depth0", "depth1_r3", "batch3", "small_maps", "nonsquare",
+                                  "distorted", "zero_ties", "nan"])
+def test_matches_the_restatement(name):
+    """bin counts 2^3 (below a wave), 3^3, 5^3 (a ragged wave), 8^3, 11^3 (ragged against 256); no edge, a chain, four leaf children, the
+    body; 1, 2 and 4 views; depth 0, 1, 10 and 3^3 recursion grids; per-sample limbs; 8x8 and 64x48 maps; distortion; rows of zeros
+    that tie; a NaN in a map"""
+    inp, ref, _ = rc.case(name)
+    _check(_run(inp), ref, name)
+    if name == "nan":
+        assert np.isnan(ref["energy"]).any()
+    if name == "zero_ties":
+        assert (ref["energy"] == 0.0).all() and (ref["bins"][:, 0] == 0).all()
+
+
+def test_reference_golden_at_16_cubed():
+    """4096 bins, the LDS-full size, B = 2: the reference's own bins and poses (tests/golden/make_golden_rpsm.py)"""
+    g = rc.golden()
+    inp = rc.attempt_inputs("g16", int(g["g16_attempt"]))
+    _check(_run(inp), dict(bins=g["g16_bins"], poses=g["g16_poses"], energy=g["g16_energy"]), "16^3 golden")
+
+
+def test_layouts_dtypes_and_distortion_zeros_bitwise():
+    inp, ref, _ = rc.case("batch3")
+    whole = _run(inp)
+    assert _same(whole, _run(inp)), "two identical calls"
+    assert _same(whole, _run(inp, as_list=True)), "a list of views"
+    V = inp["hm"].shape[1]
+    assert _same(whole, _run(inp, distortion=torch.zeros(V, 5, dtype=torch.float64, device="cuda"))), "distortion = zeros"
+    for dtype in (torch.float16, torch.bfloat16):
+        low = _dev(inp["hm"]).to(dtype)
+        assert not torch.equal(low.float(), _dev(inp["hm"]))
+        up = dict(inp, hm=low.float().cpu().numpy())
+        a, b = _run(inp, dtype=dtype), _run(up)
+        assert _same(a, b), dtype
+        assert _same(a, _run(inp, dtype=dtype, as_list=True)), dtype
+
+
+def test_sub_batches_give_the_bits_of_the_uncut_call():
+    import openmpl_amd
+    inp, ref, _ = rc.case("batch4")
+    args, kw = _args(inp)
+    whole = openmpl_amd.rpsm(*args, **kw)
+    _check(whole, ref, "batch4")
+    cut = lambda s: openmpl_amd.rpsm(args[0][s], args[1][s], args[2][s], args[3], args[4], args[5][s], args[6][s], **kw)
+    a, b = cut(slice(0, 2)), cut(slice(2, 4))
+    assert _same(whole, [torch.cat([x, y]) for x, y in zip(a, b)])
+
+
+def test_launch_count_is_the_documented_one():
+    """2 + the tree levels that have children, the same for B = 1 and B = 3 and for depth 1 and 10"""
+    from openmpl_amd import rpsm as mod
+    inp, _, _ = rc.case("batch3")
+    one = dict(inp, hm=inp["hm"][:1], center=inp["center"][:1], scale=inp["scale"][:1], root_center=inp["root_center"][:1], limb=inp["limb"][:1])
+    counts = {(B, d): _launches(lambda: _run(c, recur_depth=d))[1] for B, c in ((1, one), (3, inp)) for d in (1, 10)}
+    assert set(counts.values()) == {mod.launches()} == {7}, counts
+    for name in ("single", "chain_r3", "n3"):
+        c, _, _ = rc.case(name)
+        assert _launches(lambda: _run(c))[1] == mod.launches(c["parents"]), name
+
+
+def test_closed_loop_behind_project_points():
+    """joints -> project_points pixels -> Gaussians rendered on the device at the crop's cells -> rpsm.  The poses equal the
+    restatement's on the same maps, and the restatement's error is below half the diagonal of a first-round cell."""
+    from openmpl_amd import project_points
+    inp, _, _ = rc.case("n8")
+    B, V, J, H, W = inp["hm"].shape
+    px = project_points(_dev(inp["truth"].astype(np.float32)), _dev(inp["cams"]))
+    px = (px[0] if isinstance(px, (tuple, list)) else getattr(px, "pixels", px)).double()              # (B,V,J,2)
+    k = (inp["image_size"][0] / (200.0 * _dev(inp["scale"])[..., :1].double()))[:, :, None, :]
+    half = torch.tensor([inp["image_size"][0] * 0.5, inp["image_size"][1] * 0.5], dtype=torch.float64, device="cuda")
+    cells = ((px - _dev(inp["center"]).double()[:, :, None, :]) * k + half) * torch.tensor([W / inp["image_size"][0], H / inp["image_size"][1]], dtype=torch.float64, device="cuda")
+    yy, xx = torch.meshgrid(torch.arange(H, dtype=torch.float64, device="cuda"), torch.arange(W, dtype=torch.float64, device="cuda"), indexing="ij")
+    hm = (torch.exp(-((xx - cells[..., 0, None, None]) ** 2 + (yy - cells[..., 1, None, None]) ** 2) / 8.0) + 0.004).float()
+    loop = dict(inp, hm=hm.cpu().numpy())
+    ref = rc.solve(loop)
+    assert rc.conditions(loop, ref)
+    _check(_run(loop), ref, "closed loop")
+    err = np.linalg.norm(ref["poses"] - inp["truth"], axis=-1)
+    cell = inp["kw"]["grid_size"] / (inp["kw"]["first_nbins"] - 1)
+    print("closed loop: mean joint error %.2f mm, worst %.2f mm, half a cell diagonal %.1f mm" % (err.mean(), err.max(), 0.5 * np.sqrt(3.0) * cell))
+    assert err.max() < 0.5 * np.sqrt(3.0) * cell
