@@ -321,6 +321,15 @@ def check(rc: int, what: str):
         raise RuntimeError("%s failed: %s (code %d)" % (what, msg, rc))
 
 
+def launch(name: str, device, *args):
+    """mpl_<name>(*args, stream) with `device` current and its current stream as the last argument; a non-zero return code raises
+    under that name."""
+    import torch
+    with torch.cuda.device(device):
+        rc = getattr(load(), "mpl_" + name)(*args, torch.cuda.current_stream().cuda_stream)
+    check(rc, "mpl_" + name)
+
+
 def device_error(device: int = -1) -> bool:
     """True when a kernel of an earlier call on `device` (default: the current one) reported a lost hand-off; every
     call on that device fails with RuntimeError until clear_device_error().  Reads pinned memory, no synchronisation."""

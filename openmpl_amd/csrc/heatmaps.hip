@@ -16,24 +16,19 @@
 // then the value (-0 == 0), then the lower index -- so the result is np.argmax's whatever the reduction tree, and both forms
 // and both paths give identical outputs.  No atomics, no scratch; 16-bit maps are widened exactly.
 #include "common.hpp"
-#include "inputs.hpp"
+#include "views.hpp"
 
 namespace mpl {
 
-struct DecodeParams {
-    const void* hm[MPL_MAX_VIEWS];   // view v: (B,J,H,W) of the dtype, sample b at element b * batch_stride
-    float* poses[MPL_MAX_VIEWS];
-    float* rays[MPL_MAX_VIEWS];
-    float* centers[MPL_MAX_VIEWS];
+struct DecodeParams : HeatmapTable {
+    ViewOutputs out;
     const float* center;             // (B,V,2) or null
     const float* scale;              // (B,V,2) or null; component 1 is not read
     const double* cams;              // device (V,16) or null
     float* pixels;                   // (B,V,J,2)
     float* conf;                     // (B,V,J)
     float* coords;                   // (B,V,J,2) or null
-    long long batch_stride;          // elements
     int total;                       // B * V * J
-    int V, J, H, W;
     int post;
     double w, h;
     int norm_in, norm_cam;
@@ -47,16 +42,7 @@ inline int decode_waves_per_map(size_t map_bytes) { return map_bytes >= 65536 ? 
 template <int DT> struct HmElem { static constexpr int size = DT == MPL_HM_F32 ? 4 : 2, per_chunk = 16 / size; };
 
 template <int DT>
-__device__ __forceinline__ float hm_widen16(unsigned u) {
-    if (DT == MPL_HM_BF16) return __uint_as_float(u << 16);
-    return (float)__builtin_bit_cast(_Float16, (unsigned short)u);
-}
-
-template <int DT>
-__device__ __forceinline__ float hm_load(const void* base, size_t i) {
-    if (DT == MPL_HM_F32) return static_cast<const float*>(base)[i];
-    return hm_widen16<DT>(static_cast<const unsigned short*>(base)[i]);
-}
+__device__ __forceinline__ float hm_load(const void* base, size_t i) { return hm_fetch(base, i, DT); }
 
 template <int DT>
 __device__ __forceinline__ void hm_unpack(const uint4& q, float (&v)[HmElem<DT>::per_chunk]) {
@@ -118,7 +104,7 @@ __global__ __launch_bounds__(256) void decode_kernel(const DecodeParams p) {
     if (m >= p.total) return;                                        // whole waves (WAVES == 1) or nothing (WAVES == 4)
     const int j = m % p.J, v = (m / p.J) % p.V, b = m / (p.J * p.V);
     const int HW = p.H * p.W;
-    const char* base = static_cast<const char*>(p.hm[v]) + ((size_t)b * (size_t)p.batch_stride + (size_t)j * HW) * ES;
+    const char* base = static_cast<const char*>(p.map(b, v, j, ES));
     const size_t bytes = (size_t)HW * ES;
 
     // what the finishing lane needs besides the map is fetched now, one value per lane, and handed over after the merge: the
@@ -209,8 +195,8 @@ __global__ __launch_bounds__(256) void decode_kernel(const DecodeParams p) {
     p.conf[m] = maxval;
     if (p.cams) {
         const size_t o = ((size_t)b * p.J + j) * 3;
-        prepare_point(c, (double)fx, (double)fy, maxval, p.w, p.h, p.norm_in, p.norm_cam, p.poses[v] + o, p.rays[v] + o,
-                      j == 0 ? p.centers[v] + (size_t)b * 3 : nullptr);
+        prepare_point(c, (double)fx, (double)fy, maxval, p.w, p.h, p.norm_in, p.norm_cam, p.out.poses[v] + o, p.out.rays[v] + o,
+                      j == 0 ? p.out.centers[v] + (size_t)b * 3 : nullptr);
     }
 }
 
@@ -226,26 +212,15 @@ int launch_decode_heatmaps(const void* const* heatmaps, int dtype, long long bat
                            int post_process, const float* center, const float* scale, float* pixels, float* conf, float* coords,
                            const double* cams_dev, float img_w, float img_h, int norm_in, int norm_cam, float* const* poses,
                            float* const* rays, float* const* centers, hipStream_t s) {
-    if (!heatmaps || !pixels || !conf || B <= 0 || V <= 0 || J <= 0 || H <= 0 || W <= 0) return MPL_E_INVALID;
+    if (!pixels || !conf || B <= 0 || V <= 0 || J <= 0 || H <= 0 || W <= 0) return MPL_E_INVALID;
     if ((center != nullptr) != (scale != nullptr)) return MPL_E_INVALID;
-    if (dtype != MPL_HM_F32 && dtype != MPL_HM_F16 && dtype != MPL_HM_BF16) return MPL_E_INVALID;
     if (cams_dev && (!poses || !rays || !centers || !(img_w > 0) || !(img_h > 0))) return MPL_E_INVALID;
-    if (V > MPL_MAX_VIEWS) return MPL_E_UNSUPPORTED;
-    if ((long long)H * W > (1ll << 20)) return MPL_E_UNSUPPORTED;
-    if ((long long)B * V * J > (1ll << 30)) return MPL_E_UNSUPPORTED;
-    if (batch_stride < (long long)J * H * W) return MPL_E_INVALID;
     DecodeParams p;
-    for (int v = 0; v < MPL_MAX_VIEWS; ++v) {
-        p.hm[v] = v < V ? heatmaps[v] : nullptr;
-        if (v < V && !p.hm[v]) return MPL_E_INVALID;
-        const bool on = cams_dev && v < V;
-        p.poses[v] = on ? poses[v] : nullptr;
-        p.rays[v] = on ? rays[v] : nullptr;
-        p.centers[v] = on ? centers[v] : nullptr;
-        if (on && (!p.poses[v] || !p.rays[v] || !p.centers[v])) return MPL_E_INVALID;
-    }
+    if (const int rc = heatmap_table_fill(p, heatmaps, dtype, batch_stride, B, V, J, H, W)) return rc;
+    if ((long long)B * V * J > (1ll << 30)) return MPL_E_UNSUPPORTED;
+    if (const int rc = view_outputs_fill(p.out, poses, rays, centers, V, cams_dev != nullptr)) return rc;
     p.center = center; p.scale = scale; p.cams = cams_dev; p.pixels = pixels; p.conf = conf; p.coords = coords;
-    p.batch_stride = batch_stride; p.total = B * V * J; p.V = V; p.J = J; p.H = H; p.W = W; p.post = post_process;
+    p.total = B * V * J; p.post = post_process;
     p.w = img_w; p.h = img_h; p.norm_in = norm_in; p.norm_cam = norm_cam;
     const int waves = decode_waves_per_map((size_t)H * W * (dtype == MPL_HM_F32 ? 4 : 2));
     ProfScope prof(MPL_K_FUSE_HEAD, s);

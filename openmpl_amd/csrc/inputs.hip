@@ -8,17 +8,15 @@
 // V x (B,J,3) rays and V x (B,1,3) centers that mpl_forward consumes (150 B/pose of raw input instead of 1680 B).
 // Arithmetic is fp64 and rounded once, like the reference's float64 numpy followed by .float().
 #include "common.hpp"
-#include "inputs.hpp"
+#include "views.hpp"
 
 namespace mpl {
 
 struct PrepParams {
-    float* poses[MPL_MAX_VIEWS];
-    float* rays[MPL_MAX_VIEWS];
-    float* centers[MPL_MAX_VIEWS];
+    ViewOutputs out;
     const float* px;
     const float* conf;
-    const double* cams;   // device (V,16): fx fy cx cy | R row-major (world->camera) | t (camera centre, world)
+    const double* cams;   // device (V,16) camera records
     int B, V, J;
     double w, h;
     int norm_in, norm_cam;
@@ -31,21 +29,15 @@ __global__ __launch_bounds__(256) void prepare_inputs_kernel(const PrepParams p)
     const int j = idx % p.J, v = (idx / p.J) % p.V, b = idx / (p.J * p.V);
     const size_t o = ((size_t)b * p.J + j) * 3;
     prepare_point(p.cams + v * 16, p.px[(size_t)idx * 2], p.px[(size_t)idx * 2 + 1], p.conf ? p.conf[idx] : 1.0f, p.w, p.h, p.norm_in,
-                  p.norm_cam, p.poses[v] + o, p.rays[v] + o, j == 0 ? p.centers[v] + (size_t)b * 3 : nullptr);
+                  p.norm_cam, p.out.poses[v] + o, p.out.rays[v] + o, j == 0 ? p.out.centers[v] + (size_t)b * 3 : nullptr);
 }
 
 int launch_prepare_inputs(const float* px, const float* conf, const double* cams_dev, int B, int V, int J, float w, float h,
                           int norm_in, int norm_cam, float* const* poses, float* const* rays, float* const* centers,
                           hipStream_t s) {
-    if (!px || !cams_dev || !poses || !rays || !centers || B <= 0 || V <= 0 || V > MPL_MAX_VIEWS || J <= 0 || w <= 0 || h <= 0)
-        return MPL_E_INVALID;
+    if (!px || !cams_dev || B <= 0 || V <= 0 || J <= 0 || w <= 0 || h <= 0) return MPL_E_INVALID;
     PrepParams p;
-    for (int v = 0; v < MPL_MAX_VIEWS; ++v) {
-        p.poses[v] = v < V ? poses[v] : nullptr;
-        p.rays[v] = v < V ? rays[v] : nullptr;
-        p.centers[v] = v < V ? centers[v] : nullptr;
-        if (v < V && (!p.poses[v] || !p.rays[v] || !p.centers[v])) return MPL_E_INVALID;
-    }
+    if (const int rc = view_outputs_fill(p.out, poses, rays, centers, V)) return rc;
     p.px = px; p.conf = conf; p.cams = cams_dev;
     p.B = B; p.V = V; p.J = J; p.w = w; p.h = h; p.norm_in = norm_in; p.norm_cam = norm_cam;
     const int total = B * V * J;

@@ -24,6 +24,7 @@
 //                       (unary on each joint's own grid, pairwise by the norm between the two grids, the same inference) with the
 //                       state in LDS and no trip to the host.
 #include "common.hpp"
+#include "views.hpp"
 
 namespace mpl {
 
@@ -32,7 +33,6 @@ constexpr int RPSM_MAX_BINS = 4096;          // 16^3: a joint's energies fill 32
 constexpr int RPSM_MAX_RBINS = 64;           // 4^3
 constexpr int RPSM_EMPTY = 0x7fffffff;
 constexpr int RPSM_JG = 8;                   // joints per thread of the unary kernel
-constexpr double RPSM_Z_MIN = 1e-9;
 
 struct RpsmTree {                            // built on the host from `parents`
     signed char parent[RPSM_MAX_J];
@@ -43,8 +43,7 @@ struct RpsmTree {                            // built on the host from `parents`
     int n_levels;
 };
 
-struct RpsmParams {
-    const void* hm[MPL_MAX_VIEWS];
+struct RpsmParams : HeatmapTable {
     const float* center;
     const float* scale;
     const double* cams;
@@ -57,19 +56,10 @@ struct RpsmParams {
     float* poses;
     int* bins;
     double* energy;
-    long long batch_stride;
-    int B, V, J, H, W, dtype;
     int n, nb, rn, rnb, depth;
     double img_w, img_h, grid_size, tol;
     RpsmTree tree;
 };
-
-__device__ __forceinline__ double rpsm_fetch(const void* base, size_t i, int dt) {
-    if (dt == MPL_HM_F32) return (double)static_cast<const float*>(base)[i];
-    const unsigned u = static_cast<const unsigned short*>(base)[i];
-    if (dt == MPL_HM_BF16) return (double)__uint_as_float(u << 16);
-    return (double)(float)__builtin_bit_cast(_Float16, (unsigned short)u);
-}
 
 // np.linspace(-size / 2, size / 2, n)[i] + centre, with numpy's roundings: i * step + start in two steps, the last point the stop
 __device__ __forceinline__ double rpsm_coord(int i, int n, double size, double centre) {
@@ -90,10 +80,10 @@ __device__ __forceinline__ void rpsm_point(int bin, int n, double size, const do
 
 // the heatmap cell coordinates of a world point in view v of pose b; false where the point is not in front of the camera
 __device__ __forceinline__ bool rpsm_project(const RpsmParams& p, int b, int v, double X, double Y, double Z, double& ux, double& uy) {
-    const double* c = p.cams + (size_t)v * 16;
-    const double dx = X - c[13], dy = Y - c[14], dz = Z - c[15];
-    const double xc = c[4] * dx + c[5] * dy + c[6] * dz, yc = c[7] * dx + c[8] * dy + c[9] * dz, zc = c[10] * dx + c[11] * dy + c[12] * dz;
-    if (zc <= RPSM_Z_MIN) return false;
+    const Camera cam{p.cams + (size_t)v * 16};
+    double xc, yc, zc;
+    camera_coords(cam.c, X, Y, Z, xc, yc, zc);
+    if (zc <= CAMERA_Z_MIN) return false;
     const double y0 = xc / zc, y1 = yc / zc, r2 = y0 * y0 + y1 * y1;
     double k1 = 0.0, k2 = 0.0, k3 = 0.0, p1 = 0.0, p2 = 0.0;         // zeros: the polynomial returns (y0, y1) bit for bit
     if (p.dist) {
@@ -101,7 +91,7 @@ __device__ __forceinline__ bool rpsm_project(const RpsmParams& p, int b, int v, 
         k1 = d[0]; k2 = d[1]; k3 = d[2]; p1 = d[3]; p2 = d[4];
     }
     const double g = 1.0 + (k1 * r2 + k2 * (r2 * r2) + k3 * (r2 * r2 * r2)) + (2.0 * p1 * y1 + 2.0 * p2 * y0);
-    const double px = c[0] * (y0 * g + p2 * r2) + c[2], py = c[1] * (y1 * g + p1 * r2) + c[3];
+    const double px = cam.fx() * (y0 * g + p2 * r2) + cam.cx(), py = cam.fy() * (y1 * g + p1 * r2) + cam.cy();
     const size_t bv = ((size_t)b * p.V + v) * 2;
     const double k = p.img_w / (200.0 * (double)p.scale[bv]);
     ux = ((px - (double)p.center[bv]) * k + p.img_w * 0.5) * (double)p.W / p.img_w;
@@ -117,14 +107,9 @@ __device__ __forceinline__ double rpsm_sample(const void* map, int dt, int H, in
     if (y0 > H - 2) y0 = H - 2;
     const double tx = ux - (double)x0, ty = uy - (double)y0, sx = 1.0 - tx, sy = 1.0 - ty;
     const size_t o = (size_t)y0 * (size_t)W + (size_t)x0;
-    const double v00 = rpsm_fetch(map, o, dt), v10 = rpsm_fetch(map, o + 1, dt);              // v<x><y>
-    const double v01 = rpsm_fetch(map, o + W, dt), v11 = rpsm_fetch(map, o + W + 1, dt);
+    const double v00 = hm_fetch(map, o, dt), v10 = hm_fetch(map, o + 1, dt);                  // v<x><y>
+    const double v01 = hm_fetch(map, o + W, dt), v11 = hm_fetch(map, o + W + 1, dt);
     return ((v00 * (sx * sy) + v01 * (sx * ty)) + v10 * (tx * sy)) + v11 * (tx * ty);
-}
-
-__device__ __forceinline__ const void* rpsm_map(const RpsmParams& p, int b, int v, int j) {
-    const size_t es = p.dtype == MPL_HM_F32 ? 4 : 2;
-    return static_cast<const char*>(p.hm[v]) + ((size_t)b * (size_t)p.batch_stride + (size_t)j * (size_t)p.H * (size_t)p.W) * es;
 }
 
 // a is ahead of b: a candidate at all, then NaN above everything, then the value, then the lower index
@@ -155,7 +140,7 @@ __global__ __launch_bounds__(256) void rpsm_unary_kernel(const RpsmParams p) {
 #pragma unroll
         for (int k = 0; k < RPSM_JG; ++k) {
             const int j = jg * RPSM_JG + k;
-            if (j < p.J) acc[k] += rpsm_sample(rpsm_map(p, b, v, j), p.dtype, p.H, p.W, ux, uy);
+            if (j < p.J) acc[k] += rpsm_sample(p.map(b, v, j), p.dtype, p.H, p.W, ux, uy);
         }
     }
 #pragma unroll
@@ -310,7 +295,7 @@ __global__ __launch_bounds__(256) void rpsm_final_kernel(const RpsmParams p) {
             rpsm_point(q, rn, cur, s_pose + j * 3, X, Y, Z);
             for (int v = 0; v < p.V; ++v) {
                 double ux, uy;
-                if (rpsm_project(p, b, v, X, Y, Z, ux, uy)) acc += rpsm_sample(rpsm_map(p, b, v, j), p.dtype, p.H, p.W, ux, uy);
+                if (rpsm_project(p, b, v, X, Y, Z, ux, uy)) acc += rpsm_sample(p.map(b, v, j), p.dtype, p.H, p.W, ux, uy);
             }
             s_e[j * RPSM_MAX_RBINS + q] = acc;
         }
@@ -417,26 +402,20 @@ int launch_rpsm(const void* const* heatmaps, int dtype, long long batch_stride, 
                 const float* limb, long long limb_stride, const int* parents, int first_nbins, int recur_nbins, int recur_depth,
                 double grid_size, double tolerance, void* workspace, size_t workspace_bytes, float* poses, int* bins, double* energy,
                 int stages, hipStream_t s) {
-    if (!heatmaps || !center || !scale || !cams_dev || !root_center || !limb || !parents || !poses || !bins || !energy) return MPL_E_INVALID;
+    if (!center || !scale || !cams_dev || !root_center || !limb || !parents || !poses || !bins || !energy) return MPL_E_INVALID;
     if (B <= 0 || V <= 0 || J <= 0 || H <= 0 || W <= 0) return MPL_E_INVALID;
-    if (dtype != MPL_HM_F32 && dtype != MPL_HM_F16 && dtype != MPL_HM_BF16) return MPL_E_INVALID;
     if (!(img_w > 0) || !(img_h > 0) || !(grid_size > 0) || !(tolerance >= 0)) return MPL_E_INVALID;
     if (limb_stride != 0 && limb_stride < J) return MPL_E_INVALID;
     if (stages < 1 || stages > MPL_RPSM_ALL) return MPL_E_INVALID;
-    if (batch_stride < (long long)J * H * W) return MPL_E_INVALID;
-    if (V > MPL_MAX_VIEWS || J > RPSM_MAX_J || H < 2 || W < 2 || (long long)H * W > (1ll << 20)) return MPL_E_UNSUPPORTED;
+    RpsmParams p;
+    if (const int rc = heatmap_table_fill(p, heatmaps, dtype, batch_stride, B, V, J, H, W)) return rc;
+    if (J > RPSM_MAX_J || H < 2 || W < 2) return MPL_E_UNSUPPORTED;
     if (first_nbins < 2 || first_nbins > 16 || recur_nbins < 2 || recur_nbins > 4 || recur_depth < 0 || recur_depth > 16) return MPL_E_UNSUPPORTED;
     if (B > (1 << 20)) return MPL_E_UNSUPPORTED;
-    RpsmParams p;
     if (!rpsm_build_tree(parents, J, p.tree)) return MPL_E_INVALID;
     if (!workspace || workspace_bytes < rpsm_workspace_bytes(B, J, first_nbins)) return MPL_E_WORKSPACE;
-    for (int v = 0; v < MPL_MAX_VIEWS; ++v) {
-        p.hm[v] = v < V ? heatmaps[v] : nullptr;
-        if (v < V && !p.hm[v]) return MPL_E_INVALID;
-    }
     p.center = center; p.scale = scale; p.cams = cams_dev; p.dist = dist_dev; p.root_center = root_center; p.limb = limb;
-    p.limb_stride = limb_stride; p.poses = poses; p.bins = bins; p.energy = energy; p.batch_stride = batch_stride;
-    p.B = B; p.V = V; p.J = J; p.H = H; p.W = W; p.dtype = dtype;
+    p.limb_stride = limb_stride; p.poses = poses; p.bins = bins; p.energy = energy;
     p.n = first_nbins; p.nb = first_nbins * first_nbins * first_nbins; p.rn = recur_nbins; p.rnb = recur_nbins * recur_nbins * recur_nbins;
     p.depth = recur_depth; p.img_w = img_w; p.img_h = img_h; p.grid_size = grid_size; p.tol = tolerance;
     p.ws_energy = static_cast<double*>(workspace);

@@ -16,16 +16,15 @@
 // The one deviation: a joint at z_cam <= 1e-9 (the reference divides anyway) gets confidence 0 and pixel (0,0) and skips the
 // noise, visibility and missing-joint steps; its ray and normalised pose follow from that pixel.
 #include "common.hpp"
+#include "views.hpp"
 
 namespace mpl {
 
 struct SynthParams {
-    float* poses[MPL_MAX_VIEWS];
-    float* rays[MPL_MAX_VIEWS];
-    float* centers[MPL_MAX_VIEWS];
+    ViewOutputs out;
     mpl_synth_options o;
     const float* x3d;        // (B,J,3)
-    const double* cams;      // device (V,16): fx fy cx cy | R row-major (world->camera) | t (camera centre, world)
+    const double* cams;      // device (V,16) camera records
     const float* conf;       // (B,V,J) or null (-> 1)
     const float* rot_deg;    // (B) or null
     const float* trans;      // (B,3) or null
@@ -82,16 +81,14 @@ __global__ __launch_bounds__(256) void synthesize_views_kernel(const SynthParams
 
     // 2. projection: x_cam = R (X - t), px = (fx x / z + cx, fy y / z + cy)
     const double* c = p.cams + v * 16;
-    double fx = c[0], fy = c[1], cx = c[2], cy = c[3];
-    const double dx = X - c[13], dy = Y - c[14], dz = Z - c[15];
-    const double xc = c[4] * dx + c[5] * dy + c[6] * dz;
-    const double yc = c[7] * dx + c[8] * dy + c[9] * dz;
-    const double zc = c[10] * dx + c[11] * dy + c[12] * dz;
-    const bool front = zc > 1e-9;
+    const Camera cam{c};
+    double xc, yc, zc;
+    camera_coords(c, X, Y, Z, xc, yc, zc);
+    const bool front = zc > CAMERA_Z_MIN;
     double x = 0.0, y = 0.0, cf = 0.0;
     if (front) {
-        x = fx * xc / zc + cx;
-        y = fy * yc / zc + cy;
+        x = cam.fx() * xc / zc + cam.cx();
+        y = cam.fy() * yc / zc + cam.cy();
         cf = p.conf ? (double)p.conf[idx] : 1.0;
     }
     if (p.px_clean) {
@@ -145,32 +142,13 @@ __global__ __launch_bounds__(256) void synthesize_views_kernel(const SynthParams
         p.px[(size_t)idx * 2 + 1] = (float)y;
     }
 
-    // 6. normalisation, rays, centres: prepare_inputs_kernel on the fp64 pixel
+    // 6. normalisation, rays, centres: prepare_inputs_kernel on the fp64 pixel.  The compiler barrier makes prepare_point read the
+    // camera record again, as step 6 always has: held in registers across steps 3 to 5, R and t cost 24 VGPRs and two occupancy steps
     if (p.has_views) {
-        if (o.normalize_inputs) {
-            x = (x / o.img_w) * 2.0 - 1.0;
-            y = (y / o.img_w) * 2.0 - o.img_h / o.img_w;
-            if (o.normalize_cameras) {
-                cx = (cx / o.img_w) * 2.0 - 1.0;
-                cy = (cy / o.img_w) * 2.0 - o.img_h / o.img_w;
-                fx = fx / o.img_w * 2.0;
-                fy = fy / o.img_w * 2.0;
-            }
-        }
-        const double u0 = (x - cx) / fx, u1 = (y - cy) / fy, u2 = 1.0;
+        asm volatile("" ::: "memory");
         const size_t ob = ((size_t)b * p.J + j) * 3;
-        float* po = p.poses[v] + ob;
-        po[0] = (float)x;
-        po[1] = (float)y;
-        po[2] = (float)cf;
-        float* ro = p.rays[v] + ob;
-#pragma unroll
-        for (int d = 0; d < 3; ++d) ro[d] = (float)(u0 * c[4 + d] + u1 * c[7 + d] + u2 * c[10 + d] + c[13 + d]);   // R^T u + t
-        if (j == 0) {
-            float* co = p.centers[v] + (size_t)b * 3;
-#pragma unroll
-            for (int d = 0; d < 3; ++d) co[d] = (float)c[13 + d];
-        }
+        prepare_point(c, x, y, (float)cf, o.img_w, o.img_h, o.normalize_inputs, o.normalize_cameras, p.out.poses[v] + ob, p.out.rays[v] + ob,
+                      j == 0 ? p.out.centers[v] + (size_t)b * 3 : nullptr);
     }
 
     // 7. target
@@ -197,13 +175,7 @@ int launch_synthesize_views(const float* poses3d, const double* cams_dev, const 
     const long long total = (long long)B * V * J;
     if (total > (1ll << 36)) return MPL_E_UNSUPPORTED;
     SynthParams p;
-    for (int v = 0; v < MPL_MAX_VIEWS; ++v) {
-        const bool on = any && v < V;
-        p.poses[v] = on ? poses[v] : nullptr;
-        p.rays[v] = on ? rays[v] : nullptr;
-        p.centers[v] = on ? centers[v] : nullptr;
-        if (on && (!p.poses[v] || !p.rays[v] || !p.centers[v])) return MPL_E_INVALID;
-    }
+    if (const int rc = view_outputs_fill(p.out, poses, rays, centers, V, any)) return rc;
     p.o = *opt;
     p.x3d = poses3d; p.cams = cams_dev; p.conf = conf; p.rot_deg = rotation_deg; p.trans = translation; p.noise = noise;
     p.miss_u = missing_u; p.target = target; p.px = pixels; p.px_clean = pixels_clean; p.depth = depth;

@@ -15,6 +15,7 @@ from typing import Dict, Optional, Sequence
 import torch
 
 from . import cabi
+from ._marshal import ptr, vec3
 
 CRITERIA = {"mpjpe": cabi.CRIT_MPJPE, "weighted_mpjpe": cabi.CRIT_WEIGHTED_MPJPE, "l1": cabi.CRIT_L1, "mse": cabi.CRIT_MSE,
             "mpjpe_kadkhoda": cabi.CRIT_MPJPE_KADKHODA}
@@ -28,17 +29,6 @@ def _wrap(indices, n, what):
             raise IndexError("%s index %d is out of bounds for axis with size %d" % (what, int(k), n))     # what numpy raises
         out.append(int(k) % n)
     return out
-
-
-def _vec3(v, default):
-    if v is None:
-        return [default] * 3
-    if isinstance(v, (int, float)):
-        return [float(v)] * 3
-    v = [float(x) for x in v]
-    if len(v) != 3:
-        raise RuntimeError("scale / offset / weight_axis take 3 values")
-    return v
 
 
 class PoseEvaluator:
@@ -84,7 +74,7 @@ class PoseEvaluator:
         self._opt = cabi.EvalOptions()
         self._opt.criterion = CRITERIA[criterion]
         self._opt.has_weight_axis = int(weight_axis is not None)
-        self._opt.weight_axis[:] = _vec3(weight_axis, 1.0)
+        self._opt.weight_axis[:] = vec3(weight_axis, 1.0)
         self._opt.metre_factor = 100.0 if output_in_meter else 1.0
         self._opt.n_sel, self._opt.n_groups = S, self.n_groups
         for i, j in enumerate(self.sel):
@@ -121,15 +111,10 @@ class PoseEvaluator:
         """State of the aligned pass (only with aligned=...; the tests' hook like _alloc)."""
         self._state_aligned = torch.empty(nbytes // 8, dtype=torch.float64, device=self.device)
 
-    def _stream(self):
-        return torch.cuda.current_stream(self.device).cuda_stream
-
     def reset(self):
-        with torch.cuda.device(self.device):
-            cabi.check(self._lib.mpl_eval_reset(self._state.data_ptr(), len(self.sel), self.n_groups, self._stream()), "mpl_eval_reset")
-            if self._state_aligned is not None:
-                cabi.check(self._lib.mpl_eval_reset(self._state_aligned.data_ptr(), len(self.sel), self.n_groups, self._stream()),
-                           "mpl_eval_reset")
+        for state in (self._state, self._state_aligned):
+            if state is not None:
+                cabi.launch("eval_reset", self.device, state.data_ptr(), len(self.sel), self.n_groups)
         self._fed = 0
 
     def _pose(self, t, shape, what):
@@ -193,21 +178,15 @@ class PoseEvaluator:
             raise RuntimeError("this evaluator scores groups: update() needs the group ids")
         if self._keep is not None and self._fed + B > self.keep_poses:
             raise RuntimeError("keep_poses=%d is too small for %d samples" % (self.keep_poses, self._fed + B))
-        self._opt.scale[:] = _vec3(scale, 1.0)
-        self._opt.offset[:] = _vec3(offset, 0.0)
+        self._opt.scale[:] = vec3(scale, 1.0)
+        self._opt.offset[:] = vec3(offset, 0.0)
         self._opt.n_views = int(n_views)
         if self._opt.n_views < 1:
             raise RuntimeError("n_views >= 1")
 
-        def ptr(t):
-            return None if t is None else t.data_ptr()
-
-        with torch.cuda.device(self.device):
-            rc = self._lib.mpl_eval_accumulate(self._state.data_ptr(), C.byref(self._opt), output.data_ptr(), ptr(x1), ptr(x2),
-                                               target.data_ptr(), ptr(weight), ptr(conf_3d), ptr(group), B, J,
-                                               None if self._keep is None else self._keep[0].data_ptr(),
-                                               None if self._keep is None else self._keep[1].data_ptr(), self.keep_poses, self._stream())
-        cabi.check(rc, "mpl_eval_accumulate")
+        keep = (None, None) if self._keep is None else self._keep
+        cabi.launch("eval_accumulate", self.device, self._state.data_ptr(), C.byref(self._opt), output.data_ptr(), ptr(x1), ptr(x2),
+                    target.data_ptr(), ptr(weight), ptr(conf_3d), ptr(group), B, J, ptr(keep[0]), ptr(keep[1]), self.keep_poses)
         if self._state_aligned is not None:
             self._update_aligned(output, target, conf_3d, group, B, J)
         self._fed += B
@@ -225,20 +204,15 @@ class PoseEvaluator:
             for a in range(3):                          # no host-to-device copy)
                 torch.mul(target[..., a], sc[a], out=tgt[..., a]).add_(of[a])
             target = tgt
-        with torch.cuda.device(self.device):
-            rc = self._lib.mpl_eval_accumulate(self._state_aligned.data_ptr(), C.byref(self._opt_aligned), z.data_ptr(), None, None,
-                                               target.data_ptr(), None, None if conf_3d is None else conf_3d.data_ptr(),
-                                               None if group is None else group.data_ptr(), B, J, None, None, 0, self._stream())
-        cabi.check(rc, "mpl_eval_accumulate")
+        cabi.launch("eval_accumulate", self.device, self._state_aligned.data_ptr(), C.byref(self._opt_aligned), z.data_ptr(), None, None,
+                    target.data_ptr(), None, ptr(conf_3d), ptr(group), B, J, None, None, 0)
 
     def _report(self, state=None) -> torch.Tensor:
         """The raw report on the device (stream-ordered, no synchronisation)."""
         S = len(self.sel)
         state = self._state if state is None else state
         rep = torch.empty(self._lib.mpl_eval_report_size(S, self.n_groups), dtype=torch.float64, device=self.device)
-        with torch.cuda.device(self.device):
-            cabi.check(self._lib.mpl_eval_report(state.data_ptr(), S, self.n_groups, self.skip_mask, rep.data_ptr(), self._stream()),
-                       "mpl_eval_report")
+        cabi.launch("eval_report", self.device, state.data_ptr(), S, self.n_groups, self.skip_mask, rep.data_ptr())
         return rep
 
     def compute(self) -> Dict:

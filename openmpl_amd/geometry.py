@@ -16,6 +16,7 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 
 from . import cabi
+from ._marshal import ptr, table
 
 
 def _listed(lst, what, n=None):
@@ -66,10 +67,6 @@ def _lines(rays, centers, conf, weight=None):
     return rays, centers, conf, weight, stride, B, V, J
 
 
-def _table(lst):
-    return None if lst is None else (cabi._fp * len(lst))(*[t.data_ptr() for t in lst])
-
-
 def triangulate_rays(rays: Sequence[torch.Tensor], centers: Sequence[torch.Tensor], conf: Optional[Sequence[torch.Tensor]] = None
                      ) -> Tuple[torch.Tensor, torch.Tensor]:
     """The point closest to the V lines, weighted by the confidences: (points (B,J,3), residual (B,J)), residual the weighted
@@ -78,13 +75,9 @@ def triangulate_rays(rays: Sequence[torch.Tensor], centers: Sequence[torch.Tenso
     `points` is what PoseEvaluator.update(points, target, ...) takes."""
     rays, centers, conf, _, stride, B, V, J = _lines(rays, centers, conf)
     dev = rays[0].device
-    lib = cabi.load()
     points = torch.empty((B, J, 3), dtype=torch.float32, device=dev)
     residual = torch.empty((B, J), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.mpl_triangulate_rays(_table(rays), _table(centers), _table(conf), stride, B, V, J, points.data_ptr(),
-                                      residual.data_ptr(), torch.cuda.current_stream().cuda_stream)
-    cabi.check(rc, "mpl_triangulate_rays")
+    cabi.launch("triangulate_rays", dev, table(rays), table(centers), table(conf), stride, B, V, J, points.data_ptr(), residual.data_ptr())
     return points, residual
 
 
@@ -124,15 +117,11 @@ def triangulate_rays_robust(rays: Sequence[torch.Tensor], centers: Sequence[torc
         raise RuntimeError("min_inliers must be an integer in [2, %d views] (got %r)" % (V, min_inliers))
     rays, centers, conf, _, stride, B, V, J = _lines(rays, centers, conf)
     dev = rays[0].device
-    lib = cabi.load()
     points = torch.empty((B, J, 3), dtype=torch.float32, device=dev)
     residual = torch.empty((B, J), dtype=torch.float32, device=dev)
     inliers = torch.empty((B, V, J), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.mpl_triangulate_robust(_table(rays), _table(centers), _table(conf), stride, B, V, J, tau, cth, int(min_inliers),
-                                        points.data_ptr(), residual.data_ptr(), inliers.data_ptr(),
-                                        torch.cuda.current_stream().cuda_stream)
-    cabi.check(rc, "mpl_triangulate_robust")
+    cabi.launch("triangulate_robust", dev, table(rays), table(centers), table(conf), stride, B, V, J, tau, cth, int(min_inliers),
+                points.data_ptr(), residual.data_ptr(), inliers.data_ptr())
     return points, residual, inliers
 
 
@@ -145,13 +134,9 @@ def _epipolar(rays, centers, conf, weight, threshold):
     if weight is not None:
         w_in = torch.stack(weight, dim=1)                # (B,V,J), the layout of the errors
         w_out = torch.empty_like(w_in)
-    lib = cabi.load()
     err = torch.empty((B, V, J), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.mpl_epipolar_errors(_table(rays), _table(centers), _table(conf), stride, B, V, J, err.data_ptr(),
-                                     None if w_in is None else w_in.data_ptr(), float(threshold),
-                                     None if w_out is None else w_out.data_ptr(), torch.cuda.current_stream().cuda_stream)
-    cabi.check(rc, "mpl_epipolar_errors")
+    cabi.launch("epipolar_errors", dev, table(rays), table(centers), table(conf), stride, B, V, J, err.data_ptr(), ptr(w_in), float(threshold),
+                ptr(w_out))
     return err, w_out
 
 

@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from . import cabi
+from ._marshal import ptr, table, view_lists
 
 
 def pack_cameras(cameras, device) -> torch.Tensor:
@@ -36,18 +37,12 @@ def prepare_inputs(joints_px: torch.Tensor, conf: Optional[torch.Tensor], cams: 
     if tuple(cams.shape) != (V, 16) or cams.dtype != torch.float64 or cams.device != joints_px.device:
         raise RuntimeError("cams must be float64 (V,16) on the same device (see pack_cameras)")
     dev = joints_px.device
-    lib = cabi.load()
     joints_px = joints_px.contiguous()
     if conf is not None:
         conf = conf.reshape(B, V, J).to(torch.float32).contiguous()
-    mk = lambda *s: [torch.empty(s, dtype=torch.float32, device=dev) for _ in range(V)]
-    poses, rays, centers = mk(B, J, 3), mk(B, J, 3), mk(B, 1, 3)
-    arr = lambda lst: (cabi._fp * V)(*[t.data_ptr() for t in lst])
-    with torch.cuda.device(dev):
-        rc = lib.mpl_prepare_inputs(joints_px.data_ptr(), None if conf is None else conf.data_ptr(), cams.data_ptr(), B, V, J,
-                                    float(image_size[0]), float(image_size[1]), int(normalize_inputs), int(normalize_cameras),
-                                    arr(poses), arr(rays), arr(centers), torch.cuda.current_stream().cuda_stream)
-    cabi.check(rc, "mpl_prepare_inputs")
+    poses, rays, centers = view_lists(B, V, J, dev)
+    cabi.launch("prepare_inputs", dev, joints_px.data_ptr(), ptr(conf), cams.data_ptr(), B, V, J, float(image_size[0]), float(image_size[1]),
+                int(normalize_inputs), int(normalize_cameras), table(poses), table(rays), table(centers))
     return poses, rays, centers
 
 

@@ -11,6 +11,7 @@ from typing import Dict, Optional, Sequence
 import torch
 
 from . import cabi
+from ._marshal import ptr
 
 
 def pose_metrics(output: torch.Tensor, target: torch.Tensor, weight: Optional[torch.Tensor] = None,
@@ -42,10 +43,7 @@ def pose_metrics(output: torch.Tensor, target: torch.Tensor, weight: Optional[to
         if int(k) % J >= 32:
             raise NotImplementedError("not_consider_kp can name joints 0..31 only (a 32-bit mask in mpl_pose_metrics_ex)")
         mask |= 1 << (int(k) % J)
-    with torch.cuda.device(output.device):
-        rc = lib.mpl_pose_metrics_ex(output.data_ptr(), target.data_ptr(), None if weight is None else weight.data_ptr(), B, J,
-                                     sc, of, mask, res.data_ptr(), torch.cuda.current_stream().cuda_stream)
-    cabi.check(rc, "mpl_pose_metrics")
+    cabi.launch("pose_metrics_ex", output.device, output.data_ptr(), target.data_ptr(), ptr(weight), B, J, sc, of, mask, res.data_ptr())
     # NaN poses of a forward that lost a hand-off would be SKIPPED by the nansum / nanmean semantics of the reference's metrics
     # and score as zero error: the C entry refuses while the device's error word is set, the kernel writes NaN results when
     # the failing forward is still in flight on this stream, and a failure that has already been reported raises here

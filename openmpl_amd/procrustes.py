@@ -12,7 +12,8 @@ from typing import NamedTuple, Optional, Sequence
 import torch
 
 from . import cabi
-from .evaluate import _vec3, _wrap
+from ._marshal import ptr, vec3
+from .evaluate import _wrap
 
 REFLECTION = {"best": cabi.REFLECT_BEST, False: cabi.REFLECT_OFF, True: cabi.REFLECT_ON}
 
@@ -63,16 +64,10 @@ def _checked(pred, target, conf, joints):
 
 def _launch(pred, target, conf, sel, scaling, reflection, scale3, offset3, B, J, aligned, d, rotation, scale, translation):
     """mpl_procrustes_align on the current stream of pred's device; outputs are tensors or None."""
-    def ptr(t):
-        return None if t is None else t.data_ptr()
-
     sel_c = None if sel is None else (C.c_int * len(sel))(*sel)
-    with torch.cuda.device(pred.device):
-        rc = cabi.load().mpl_procrustes_align(pred.data_ptr(), target.data_ptr(), ptr(conf), sel_c, 0 if sel is None else len(sel),
-                                              (C.c_float * 3)(*scale3), (C.c_float * 3)(*offset3), int(bool(scaling)), reflection, B, J,
-                                              ptr(aligned), ptr(d), ptr(rotation), ptr(scale), ptr(translation),
-                                              torch.cuda.current_stream().cuda_stream)
-    cabi.check(rc, "mpl_procrustes_align")
+    cabi.launch("procrustes_align", pred.device, pred.data_ptr(), target.data_ptr(), ptr(conf), sel_c, 0 if sel is None else len(sel),
+                (C.c_float * 3)(*scale3), (C.c_float * 3)(*offset3), int(bool(scaling)), reflection, B, J, ptr(aligned), ptr(d), ptr(rotation),
+                ptr(scale), ptr(translation))
 
 
 def procrustes_align(pred: torch.Tensor, target: torch.Tensor, conf: Optional[torch.Tensor] = None,
@@ -86,7 +81,7 @@ def procrustes_align(pred: torch.Tensor, target: torch.Tensor, conf: Optional[to
     A pose with fewer than 3 joints taking part, with all its points equal, or with collinear points is NaN in every output.
     Coplanar points under reflection="best" give the proper rotation (det +1), where numpy's sign is arbitrary."""
     mode = _reflection(reflection)
-    scale3, offset3 = _vec3(scale, 1.0), _vec3(offset, 0.0)
+    scale3, offset3 = vec3(scale, 1.0), vec3(offset, 0.0)
     pred, target, conf, sel, B, J = _checked(pred, target, conf, joints)
     dev = pred.device
     out = ProcrustesResult(torch.empty((B, J, 3), dtype=torch.float32, device=dev), torch.empty((B,), dtype=torch.float32, device=dev),

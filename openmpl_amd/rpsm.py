@@ -15,7 +15,7 @@ from typing import NamedTuple, Optional, Sequence, Tuple, Union
 import torch
 
 from . import cabi
-from .heatmaps import _DTYPES, _in_place
+from ._marshal import dtypes_and_devices, heatmap_shapes, heatmap_table, named_shapes, ptr
 
 # lib/multiviews/body.py:17-33 (HumanBody.get_skeleton) restated as parents: root, rhip, rkne, rank, lhip, lkne, lank, belly, neck,
 # nose, head, lsho, lelb, lwri, rsho, relb, rwri
@@ -62,22 +62,7 @@ def launches(parents: Optional[Sequence[int]] = None) -> int:
 def _check(heatmaps, center, scale, cams, image_size, root_center, limb_length, parents, first_nbins, recur_nbins, recur_depth,
            grid_size, tolerance, distortion):
     """Shapes and the envelope first (ValueError, nothing loaded), then dtypes, then devices."""
-    if isinstance(heatmaps, torch.Tensor):
-        if heatmaps.ndim != 5 or min(heatmaps.shape) < 1:
-            raise ValueError("heatmaps: expected one (B,V,J,H,W) tensor or a list of V (B,J,H,W) tensors, got shape %s" % (tuple(heatmaps.shape),))
-        B, V, J, H, W = heatmaps.shape
-        views, maps = None, [heatmaps]
-    else:
-        if not isinstance(heatmaps, (list, tuple)) or len(heatmaps) == 0 or not all(isinstance(t, torch.Tensor) for t in heatmaps):
-            raise ValueError("heatmaps must be one (B,V,J,H,W) tensor or a non-empty list of tensors, one per view")
-        views = maps = list(heatmaps)
-        V = len(views)
-        if views[0].ndim != 4 or min(views[0].shape) < 1:
-            raise ValueError("heatmaps[0]: expected shape (B,J,H,W), got %s" % (tuple(views[0].shape),))
-        B, J, H, W = views[0].shape
-        for v, t in enumerate(views):
-            if tuple(t.shape) != (B, J, H, W):
-                raise ValueError("heatmaps[%d]: expected shape %s, got %s" % (v, (B, J, H, W), tuple(t.shape)))
+    views, maps, B, V, J, H, W = heatmap_shapes(heatmaps, ValueError)
     if parents is None:
         if J != len(HUMAN_BODY_PARENTS):
             raise ValueError("the default tree has %d joints, the heatmaps %d: pass parents" % (len(HUMAN_BODY_PARENTS), J))
@@ -108,23 +93,8 @@ def _check(heatmaps, center, scale, cams, image_size, root_center, limb_length, 
              ("root_center", root_center, (B, 3), torch.float32), ("limb_length", limb_length, tuple(limb_length.shape), torch.float32)]
     if distortion is not None:
         named.append(("distortion", distortion, (V, 5), torch.float64))
-    for what, t, shape, _ in named:
-        if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape:
-            raise ValueError("%s: expected a tensor of shape %s, got %s" % (what, shape, tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__))
-    # dtypes
-    for v, t in enumerate(maps):
-        if t.dtype not in _DTYPES or t.dtype != maps[0].dtype:
-            raise ValueError("heatmaps must be float32, float16 or bfloat16, all alike (%s is %s)" % ("heatmaps" if views is None else "heatmaps[%d]" % v, t.dtype))
-    for what, t, _, want in named:
-        if t.dtype != want:
-            raise ValueError("%s must be %s (is %s)%s" % (what, want, t.dtype, " (see pack_cameras)" if what == "cams" else ""))
-    # devices
-    dev = maps[0].device
-    for what, t in [("heatmaps" if views is None else "heatmaps[%d]" % v, t) for v, t in enumerate(maps)] + [(n, t) for n, t, _, _ in named]:
-        if t.device.type != "cuda":
-            raise RuntimeError("rpsm has no CPU path: %s must live on a GPU" % what)
-        if t.device != dev:
-            raise RuntimeError("%s is on %s, the heatmaps on %s" % (what, t.device, dev))
+    named_shapes(named, ValueError)
+    dtypes_and_devices(views, maps, named, "rpsm", ValueError)
     return views, parents, levels, B, V, J, H, W
 
 
@@ -155,16 +125,7 @@ def rpsm(heatmaps: Union[torch.Tensor, Sequence[torch.Tensor]], center: torch.Te
     (_stages, _workspace: for tools/rpsm_prof.py, which issues the stages of a call one by one on a buffer it keeps.)"""
     views, parents, _, B, V, J, H, W = _check(heatmaps, center, scale, cams, image_size, root_center, limb_length, parents, first_nbins,
                                               recur_nbins, recur_depth, grid_size, tolerance, distortion)
-    inner = (J, H, W)
-    if views is None:
-        hm = heatmaps if _in_place(heatmaps, inner) else heatmaps.contiguous()
-        keep = [hm]
-        ptrs = [hm.data_ptr() + v * hm.stride(1) * hm.element_size() for v in range(V)]
-    else:
-        ok = all(_in_place(t, inner) for t in views) and (B == 1 or len({t.stride(0) for t in views}) == 1)
-        keep = views if ok else [t.contiguous() for t in views]
-        ptrs = [t.data_ptr() for t in keep]
-    stride = keep[0].stride(0) if B > 1 else J * H * W
+    keep, hm, stride, dtype = heatmap_table(heatmaps, views, B, V, J, H, W)
     dev = keep[0].device
     lib = cabi.load()
     center, scale, cams, root_center, limb_length = (t.contiguous() for t in (center, scale, cams, root_center, limb_length))
@@ -176,13 +137,10 @@ def rpsm(heatmaps: Union[torch.Tensor, Sequence[torch.Tensor]], center: torch.Te
     poses = torch.empty((B, J, 3), dtype=torch.float32, device=dev)
     bins = torch.empty((B, 1 + recur_depth, J), dtype=torch.int32, device=dev)
     energy = torch.empty((B,), dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.mpl_rpsm((cabi._fp * V)(*ptrs), _DTYPES[keep[0].dtype], stride, B, V, J, H, W, center.data_ptr(), scale.data_ptr(),
-                          cams.data_ptr(), None if distortion is None else distortion.data_ptr(), float(image_size[0]), float(image_size[1]),
-                          root_center.data_ptr(), limb_length.data_ptr(), J if limb_length.ndim == 2 else 0, (cabi.C.c_int * J)(*parents),
-                          first_nbins, recur_nbins, recur_depth, float(grid_size), float(tolerance), ws.data_ptr(), ws.numel(),
-                          poses.data_ptr(), bins.data_ptr(), energy.data_ptr(), int(_stages), torch.cuda.current_stream().cuda_stream)
-    cabi.check(rc, "mpl_rpsm")
+    cabi.launch("rpsm", dev, hm, dtype, stride, B, V, J, H, W, center.data_ptr(), scale.data_ptr(), cams.data_ptr(), ptr(distortion),
+                float(image_size[0]), float(image_size[1]), root_center.data_ptr(), limb_length.data_ptr(), J if limb_length.ndim == 2 else 0,
+                (cabi.C.c_int * J)(*parents), first_nbins, recur_nbins, recur_depth, float(grid_size), float(tolerance), ws.data_ptr(),
+                ws.numel(), poses.data_ptr(), bins.data_ptr(), energy.data_ptr(), int(_stages))
     return RPSMResult(poses, bins, energy)
 
 

@@ -17,6 +17,7 @@ from typing import Optional, Sequence, Tuple
 import torch
 
 from . import cabi, detrng
+from ._marshal import ptr, table, vec3, view_lists
 
 SynthViews = namedtuple("SynthViews", "poses rays centers target pixels pixels_clean")
 
@@ -26,19 +27,6 @@ def _keys(seed):
     """the six stream keys of a seed, in the order of the key_* fields of mpl_synth_options"""
     return tuple(int(detrng._stream_key(seed, name, lane)) for name, lane in (("synth.rot", 0), ("synth.room", 0), ("synth.room", 1),
                                                                               ("synth.noise", 0), ("synth.noise", 1), ("synth.missing", 0)))
-
-
-def _vec3(v, default, what):
-    if v is None:
-        return [default] * 3
-    if isinstance(v, torch.Tensor):
-        v = v.detach().cpu().reshape(-1).tolist()
-    elif isinstance(v, (int, float)):
-        v = [float(v)] * 3
-    v = [float(x) for x in v]
-    if len(v) != 3:
-        raise RuntimeError("%s takes 3 values" % what)
-    return v
 
 
 def _optional(t, shape, what, dev):
@@ -62,10 +50,6 @@ def _check_scene(poses3d, cams, fn):
     if cams.shape[0] > cabi.MPL_MAX_VIEWS:
         raise RuntimeError("at most %d views, got %d" % (cabi.MPL_MAX_VIEWS, cams.shape[0]))
     return poses3d.shape[0], cams.shape[0], poses3d.shape[1]
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
 
 
 def synthesize_views(poses3d: torch.Tensor, cams: torch.Tensor, image_size: Tuple[float, float], *, seed: int = 0, first_index: int = 0,
@@ -97,7 +81,7 @@ def synthesize_views(poses3d: torch.Tensor, cams: torch.Tensor, image_size: Tupl
     w, h = float(image_size[0]), float(image_size[1])
     if not (w > 0 and h > 0):
         raise RuntimeError("image_size must be positive, got %r" % (tuple(image_size),))
-    scale, offset = _vec3(target_scale, 1.0, "target_scale"), _vec3(target_offset, 0.0, "target_offset")
+    scale, offset = vec3(target_scale, 1.0, "target_scale takes 3 values"), vec3(target_offset, 0.0, "target_offset takes 3 values")
     if any(s == 0.0 or s != s for s in scale):
         raise RuntimeError("target_scale must not hold a zero")
     if room is not None:
@@ -122,19 +106,13 @@ def synthesize_views(poses3d: torch.Tensor, cams: torch.Tensor, image_size: Tupl
     o.key_rot, o.key_room_x, o.key_room_y, o.key_noise0, o.key_noise1, o.key_missing = _keys(int(seed))
     o.first_index = int(first_index)
 
-    lib = cabi.load()
     poses3d, cams = poses3d.contiguous(), cams.contiguous()
-    mk = lambda *s: [torch.empty(s, dtype=torch.float32, device=dev) for _ in range(V)]
-    poses, rays, centers = mk(B, J, 3), mk(B, J, 3), mk(B, 1, 3)
+    poses, rays, centers = view_lists(B, V, J, dev)
     target = torch.empty((B, J, 3), dtype=torch.float32, device=dev)
     pixels = torch.empty((B, V, J, 2), dtype=torch.float32, device=dev) if return_pixels else None
     clean = torch.empty((B, V, J, 2), dtype=torch.float32, device=dev) if return_pixels else None
-    arr = lambda lst: (cabi._fp * V)(*[t.data_ptr() for t in lst])
-    with torch.cuda.device(dev):
-        rc = lib.mpl_synthesize_views(poses3d.data_ptr(), cams.data_ptr(), C.byref(o), _ptr(conf), _ptr(rotation_deg), _ptr(translation),
-                                      _ptr(noise), _ptr(missing_u), B, V, J, arr(poses), arr(rays), arr(centers), target.data_ptr(),
-                                      _ptr(pixels), _ptr(clean), None, torch.cuda.current_stream().cuda_stream)
-    cabi.check(rc, "mpl_synthesize_views")
+    cabi.launch("synthesize_views", dev, poses3d.data_ptr(), cams.data_ptr(), C.byref(o), ptr(conf), ptr(rotation_deg), ptr(translation),
+                ptr(noise), ptr(missing_u), B, V, J, table(poses), table(rays), table(centers), target.data_ptr(), ptr(pixels), ptr(clean), None)
     return SynthViews(poses, rays, centers, target, pixels, clean)
 
 
@@ -147,12 +125,9 @@ def project_points(points3d: torch.Tensor, cams: torch.Tensor) -> Tuple[torch.Te
     o = cabi.SynthOptions()
     o.img_w = o.img_h = 1.0
     o.target_scale[:] = [1.0] * 3
-    lib = cabi.load()
     points3d, cams = points3d.contiguous(), cams.contiguous()
     pixels = torch.empty((B, V, J, 2), dtype=torch.float32, device=dev)
     depth = torch.empty((B, V, J), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.mpl_synthesize_views(points3d.data_ptr(), cams.data_ptr(), C.byref(o), None, None, None, None, None, B, V, J, None, None,
-                                      None, None, None, pixels.data_ptr(), depth.data_ptr(), torch.cuda.current_stream().cuda_stream)
-    cabi.check(rc, "mpl_synthesize_views")
+    cabi.launch("synthesize_views", dev, points3d.data_ptr(), cams.data_ptr(), C.byref(o), None, None, None, None, None, B, V, J, None, None,
+                None, None, None, pixels.data_ptr(), depth.data_ptr())
     return pixels, depth

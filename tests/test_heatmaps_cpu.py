@@ -128,22 +128,31 @@ def _maps(B=2, V=2, J=3, H=8, W=8, dtype=torch.float32):
 
 
 def test_wrapper_complaints_need_no_gpu():
-    """shapes, then dtypes, then devices: on CPU tensors a well-formed call gets as far as the device complaint"""
+    """shapes, then dtypes, then devices: on CPU tensors a well-formed call gets as far as the device complaint.  The complaints
+    about the heatmaps' structure and dtype are one rule for both entry points: openmpl_amd.rpsm, given the same heatmaps and
+    otherwise valid CPU arguments, raises the same text as a ValueError."""
     d = openmpl_amd.decode_heatmaps
     box = lambda: torch.zeros((2, 2, 2))
     cams = torch.zeros((2, 16), dtype=torch.float64)
 
-    def complains(text, *a, exc=RuntimeError, **kw):
+    def rpsm_too(text, heatmaps, B, V, J):
+        with pytest.raises(ValueError, match=text):
+            openmpl_amd.rpsm(heatmaps, torch.zeros((B, V, 2)), torch.ones((B, V, 2)), torch.zeros((V, 16), dtype=torch.float64), (256.0, 256.0),
+                             torch.zeros((B, 3)), torch.ones(J), parents=[-1] + [0] * (J - 1))
+
+    def complains(text, *a, exc=RuntimeError, both=None, **kw):
         with pytest.raises(exc, match=text):
             d(*a, **kw)
+        if both:
+            rpsm_too(text, *a, *both)
     # shapes
-    complains("one \\(B,V,J,H,W\\) tensor or a non-empty list", [])
-    complains("one \\(B,V,J,H,W\\) tensor or a non-empty list", [np.zeros((2, 3, 8, 8))])
-    complains("one \\(B,V,J,H,W\\) tensor or a non-empty list", None)
-    complains("expected one \\(B,V,J,H,W\\) tensor", torch.zeros((2, 3, 8, 8)))
-    complains("expected one \\(B,V,J,H,W\\) tensor", torch.zeros((2, 2, 3, 0, 8)))
-    complains("heatmaps\\[0\\]: expected shape \\(B,J,H,W\\)", [torch.zeros((2, 2, 3, 8, 8))])
-    complains("heatmaps\\[1\\]: expected shape \\(2, 3, 8, 8\\), got \\(2, 3, 8, 7\\)", [_maps()[0], torch.zeros((2, 3, 8, 7))])
+    complains("one \\(B,V,J,H,W\\) tensor or a non-empty list", [], both=(2, 2, 3))
+    complains("one \\(B,V,J,H,W\\) tensor or a non-empty list", [np.zeros((2, 3, 8, 8))], both=(2, 2, 3))
+    complains("one \\(B,V,J,H,W\\) tensor or a non-empty list", None, both=(2, 2, 3))
+    complains("expected one \\(B,V,J,H,W\\) tensor", torch.zeros((2, 3, 8, 8)), both=(2, 2, 3))
+    complains("expected one \\(B,V,J,H,W\\) tensor", torch.zeros((2, 2, 3, 0, 8)), both=(2, 2, 3))
+    complains("heatmaps\\[0\\]: expected shape \\(B,J,H,W\\)", [torch.zeros((2, 2, 3, 8, 8))], both=(2, 2, 3))
+    complains("heatmaps\\[1\\]: expected shape \\(2, 3, 8, 8\\), got \\(2, 3, 8, 7\\)", [_maps()[0], torch.zeros((2, 3, 8, 7))], both=(2, 2, 3))
     complains("center and scale go together \\(got only center\\)", _maps(), box())
     complains("center and scale go together \\(got only scale\\)", _maps(), None, box())
     complains("center: expected a tensor of shape \\(2, 2, 2\\)", _maps(), torch.zeros((2, 2)), box())
@@ -154,10 +163,10 @@ def test_wrapper_complaints_need_no_gpu():
     complains("at most 32 views", [torch.zeros((1, 1, 2, 2))] * 33, exc=NotImplementedError)
     complains("2\\^20 values per map", torch.zeros((1, 1, 1, 1024, 1025), dtype=torch.bfloat16), exc=NotImplementedError)
     # dtypes: a shape complaint comes first
-    complains("heatmaps\\[1\\]: expected shape", [_maps()[0], torch.zeros((2, 3, 8, 7), dtype=torch.float64)])
-    complains("float32, float16 or bfloat16, all alike \\(heatmaps\\[0\\] is torch.float64\\)", _maps(dtype=torch.float64))
-    complains("all alike \\(heatmaps\\[1\\] is torch.float16\\)", [_maps()[0], _maps(dtype=torch.float16)[0]])
-    complains("all alike \\(heatmaps is torch.int32\\)", torch.zeros((1, 1, 1, 2, 2), dtype=torch.int32))
+    complains("heatmaps\\[1\\]: expected shape", [_maps()[0], torch.zeros((2, 3, 8, 7), dtype=torch.float64)], both=(2, 2, 3))
+    complains("float32, float16 or bfloat16, all alike \\(heatmaps\\[0\\] is torch.float64\\)", _maps(dtype=torch.float64), both=(2, 2, 3))
+    complains("all alike \\(heatmaps\\[1\\] is torch.float16\\)", [_maps()[0], _maps(dtype=torch.float16)[0]], both=(2, 2, 3))
+    complains("all alike \\(heatmaps is torch.int32\\)", torch.zeros((1, 1, 1, 2, 2), dtype=torch.int32), both=(1, 1, 1))
     complains("center must be torch.float32", _maps(), box().double(), box())
     complains("scale must be torch.float32", _maps(), box(), box().half())
     complains("cams must be torch.float64 .*pack_cameras", _maps(), cams=cams.float(), image_size=(1000, 1000))

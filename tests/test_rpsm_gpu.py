@@ -82,10 +82,15 @@ def test_reference_golden_at_16_cubed():
 
 
 def test_layouts_dtypes_and_distortion_zeros_bitwise():
+    from openmpl_amd import rpsm as mod_rpsm
     inp, ref, _ = rc.case("batch3")
     whole = _run(inp)
     assert _same(whole, _run(inp)), "two identical calls"
     assert _same(whole, _run(inp, as_list=True)), "a list of views"
+    args, kw = _args(inp)
+    t = args[0]                                                         # B = 3: the batch stride is read
+    assert _same(whole, mod_rpsm(list(t.unbind(1)), *args[1:], **kw)), "views of the one tensor, at its batch stride"
+    assert _same(whole, mod_rpsm(t.transpose(0, 1).contiguous().transpose(0, 1), *args[1:], **kw)), "(V,B,...) memory"
     V = inp["hm"].shape[1]
     assert _same(whole, _run(inp, distortion=torch.zeros(V, 5, dtype=torch.float64, device="cuda"))), "distortion = zeros"
     for dtype in (torch.float16, torch.bfloat16):
