@@ -31,6 +31,8 @@
  *   mpl_procrustes_align   lib/utils/pose_utils.py:61-143 (PoseUtils.procrustes, one numpy SVD per pose)
  *   mpl_synthesize_views   lib/dataset/multiview_amass_h36m_mpl.py:317-342 + joints_dataset_mpl.py:588-774 (synthetic detections)
  *   mpl_decode_heatmaps    lib/core/inference.py:22-81 (get_max_preds, get_final_preds) + lib/utils/transforms.py:51-94
+ *   mpl_decode_heatmaps_ex the same with a sub-pixel peak: the intent of lib/core/inference.py:84-134 (find_tensor_peak_batch)
+ *   mpl_render_heatmaps    lib/dataset/joints_dataset_mpl.py:828-870 (generate_heatmap)
  *   mpl_rpsm               lib/multiviews/pictorial.py:18-247 (rpsm, recursive_infer, infer, compute_unary_term, compute_grid)
  */
 #ifndef MPL_HIP_H_
@@ -404,6 +406,63 @@ int mpl_decode_heatmaps(const void *const *heatmaps, int dtype, long long batch_
                         int height, int width, int post_process, const float *center, const float *scale, float *pixels,
                         float *conf, float *coords, const double *cams_dev, float img_w, float img_h, int normalize_inputs,
                         int normalize_cameras, float *const *poses, float *const *rays, float *const *centers, void *stream);
+
+/* Sub-pixel decoding: mpl_decode_heatmaps with step b replaced by a refinement of the integer peak (x0, y0).  `refine`:
+ * MPL_REFINE_NONE is mpl_decode_heatmaps itself, same kernels and same bits (radius and threshold are not looked at);
+ * MPL_REFINE_GAUSSIAN and MPL_REFINE_CENTROID exclude post_process.  A refinement applies only where 0 < maxval < inf; elsewhere
+ * the coordinates are those of the plain decode ((0,0) for a non-positive or NaN peak, the integer peak for +inf).  The offset d
+ * is fp64 on the exactly widened values, and x0 + d is rounded to fp32 once -> coords; steps c and d follow on that coordinate.
+ * MPL_REFINE_GAUSSIAN: per axis the three values f-, f0, f+ on the peak's row (x) or column (y): a = ln f0 - ln f+,
+ * b = ln f0 - ln f-, d = (b - a) / (2 (a + b)), exact for a Gaussian of any sigma and within +/-0.5 because f0 is the maximum.
+ * d = 0 on an axis whose peak coordinate is 0 or the last one, where a neighbour is not positive and finite, or where a + b == 0.
+ * MPL_REFINE_CENTROID: what find_tensor_peak_batch (lib/core/inference.py:84-134) means to compute.  Over the window
+ * (x0 + i, y0 + j), |i|, |j| <= radius (1..8): w = the value where it is above `threshold` and inside the map, else 0
+ * (F.threshold, padding_mode='zeros'); S = sum w + 2.22e-16; d = (sum w i / S, sum w j / S).  Deviations from the reference's
+ * lines: the row is idx / W in integers (the reference divides truly), and the samples sit on the integer cells, the
+ * align_corners=True reading of its normalize(), so an integer radius needs no interpolation; pix2coord is not applied, step c is
+ * the way back to pixels.  The window is spread over the 64 lanes of the finishing wave and summed in a fixed order: the one-wave
+ * and the four-wave form, every layout and every run give the same bits.
+ * MPL_E_INVALID, besides those of mpl_decode_heatmaps: refine outside 0..2; a refinement together with post_process; with
+ * MPL_REFINE_CENTROID a radius outside 1..8 or a NaN threshold.  All before any launch. */
+#define MPL_REFINE_NONE 0
+#define MPL_REFINE_GAUSSIAN 1
+#define MPL_REFINE_CENTROID 2
+int mpl_decode_heatmaps_ex(const void *const *heatmaps, int dtype, long long batch_stride, int batch, int views, int joints,
+                           int height, int width, int post_process, const float *center, const float *scale, float *pixels,
+                           float *conf, float *coords, const double *cams_dev, float img_w, float img_h, int normalize_inputs,
+                           int normalize_cameras, float *const *poses, float *const *rays, float *const *centers, int refine,
+                           int radius, double threshold, void *stream);
+
+/* ---- heatmaps rendered from 2D joints, csrc/heatmap_render.hip: the producer in front of mpl_decode_heatmaps and mpl_rpsm, in
+ * place of generate_heatmap (lib/dataset/joints_dataset_mpl.py:828-870, numpy, one joint at a time).  One launch, one wave per map.
+ * The cell m of joint (b,v,j), fp64 on the fp32 inputs: with center / scale (device fp32 (B,V,2), both or neither)
+ * m = (pixel - center[b,v]) / k + (W/2, H/2), k = scale[b,v,0] * 200 / W, the exact inverse of mpl_decode_heatmaps step c; with
+ * stride_x, stride_y > 0 (both or neither, not together with center) m = pixel / stride, the reference's feat_stride; with neither
+ * m = pixel.  cells (B,V,J,2) = m rounded once.
+ * MPL_RENDER_REFERENCE is generate_heatmap: mu = trunc(m + 0.5) (towards zero, Python's int); weight = conf (NULL: 1), 0 when the
+ * patch mu +/- 3 sigma lies wholly outside the map (mu - 3 sigma >= size or mu + 3 sigma + 1 < 0 on an axis); where
+ * weight > 0.5 the cells of the patch inside the map hold exp(-(dx^2 + dy^2) / (2 sigma^2)) at integer dx, dy; every other cell is
+ * 0.  3 * sigma must be an integer.
+ * MPL_RENDER_SUBPIXEL: conf * exp(-((x - mx)^2 + (y - my)^2) / (2 sigma^2)) on every cell, weight = conf; a joint whose conf is not
+ * above 0 gets a zero map and weight 0.
+ * Both: a cell m that is not finite or beyond +/-2^30 gives a zero map and weight 0 (a deviation: the reference raises).  A value is
+ * the fp64 product of its two separable factors, rounded once to `dtype`, denormals kept.  noise_level = a > 0 adds a * u to every
+ * cell of every map (zero maps included) before that rounding, u = draw (((first_index + b) * V + v) * J + j) * H * W + y * W + x
+ * of the stream noise_key (see mpl_synthesize_views for the draw): a run cut into batches is the uncut run; a == 0 draws nothing.
+ * heatmaps / dtype / batch_stride: the table of mpl_decode_heatmaps, written in place; the caller sees to it that the maps do not
+ * overlap.  A map whose base address and byte size are multiples of 16 is written with 16-byte stores, any other element by
+ * element; the bits are the same.  pixels (B,V,J,2), conf (B,V,J) or NULL: device fp32.  weight (B,V,J), cells (B,V,J,2): fp32 out.
+ * MPL_E_INVALID: heatmaps, one of its first `views` entries, pixels, weight or cells NULL; a non-positive size; center without
+ * scale or the reverse; one stride without the other, a negative or NaN stride, strides together with center; an unknown dtype or
+ * mode; sigma not in (0, 1e6]; 3 * sigma not an integer in MPL_RENDER_REFERENCE; noise_level negative or NaN; first_index < 0;
+ * batch_stride < J*H*W.  MPL_E_UNSUPPORTED: views > MPL_MAX_VIEWS, H*W > 2^20, batch*views*joints > 2^30.  All before any launch.
+ * Stream-ordered, never synchronises; neither looks at nor sets the device error word. */
+#define MPL_RENDER_REFERENCE 0
+#define MPL_RENDER_SUBPIXEL 1
+int mpl_render_heatmaps(void *const *heatmaps, int dtype, long long batch_stride, int batch, int views, int joints, int height,
+                        int width, const float *pixels, const float *conf, const float *center, const float *scale,
+                        double stride_x, double stride_y, int mode, double sigma, double noise_level, uint64_t noise_key,
+                        long long first_index, float *weight, float *cells, void *stream);
 
 /* ---- recursive pictorial structure model, csrc/rpsm.hip: a 3D pose from the WHOLE heatmaps of all views, in place of
  * lib/multiviews/pictorial.py (numpy, fp64; one pose at a time, a dense nbins x nbins product per edge: 11 s per pose at 16^3 bins).

@@ -24,9 +24,9 @@ def __getattr__(name):
     if name in ("synthesize_views", "project_points"):
         from . import synth
         return getattr(synth, name)
-    if name == "decode_heatmaps":
-        from .heatmaps import decode_heatmaps
-        return decode_heatmaps
+    if name in ("decode_heatmaps", "render_heatmaps"):
+        from . import heatmaps
+        return getattr(heatmaps, name)
     if name == "rpsm":
         # the module is callable (openmpl_amd.rpsm(...)); importing it binds this attribute for good
         import importlib

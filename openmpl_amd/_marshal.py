@@ -92,17 +92,23 @@ def _in_place(t, inner):
     return tuple(t.stride()[-3:]) == (H * W, W, 1) and (t.shape[0] == 1 or t.stride(0) >= J * H * W)
 
 
-def heatmap_table(heatmaps, views, B, V, J, H, W):
+def heatmap_table(heatmaps, views, B, V, J, H, W, writable=False):
     """-> (keep, table, batch stride in elements, dtype code): the tensors the table points into and the first three arguments of
-    mpl_decode_heatmaps / mpl_rpsm.  Nothing is copied unless a (J,H,W) block is not dense or the views differ in their batch
-    stride."""
+    mpl_decode_heatmaps / mpl_rpsm / mpl_render_heatmaps.  Nothing is copied unless a (J,H,W) block is not dense or the views
+    differ in their batch stride.  writable: the table is written (render_heatmaps' out=), so a copy would be of no use and the
+    views of one tensor must not overlap either: such an argument raises RuntimeError."""
     inner = (J, H, W)
     if views is None:
-        hm = heatmaps if _in_place(heatmaps, inner) else heatmaps.contiguous()
+        ok = _in_place(heatmaps, inner) and (not writable or V == 1 or heatmaps.stride(1) >= J * H * W)
+        if writable and not ok:
+            raise RuntimeError("out must be written where it lies: every (J,H,W) block dense, samples and views at non-overlapping strides")
+        hm = heatmaps if ok else heatmaps.contiguous()
         keep = [hm]
         ptrs = [hm.data_ptr() + v * hm.stride(1) * hm.element_size() for v in range(V)]
     else:
         ok = all(_in_place(t, inner) for t in views) and (B == 1 or len({t.stride(0) for t in views}) == 1)
+        if writable and not ok:
+            raise RuntimeError("out must be written where it lies: every (J,H,W) block dense, samples of all views at one non-overlapping stride")
         keep = views if ok else [t.contiguous() for t in views]
         ptrs = [t.data_ptr() for t in keep]
     stride = keep[0].stride(0) if B > 1 else J * H * W

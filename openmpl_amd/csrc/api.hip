@@ -824,6 +824,27 @@ int mpl_decode_heatmaps(const void* const* heatmaps, int dtype, long long batch_
                                   centers, (hipStream_t)stream);
 }
 
+int mpl_decode_heatmaps_ex(const void* const* heatmaps, int dtype, long long batch_stride, int batch, int views, int joints, int height,
+                           int width, int post_process, const float* center, const float* scale, float* pixels, float* conf,
+                           float* coords, const double* cams_dev, float img_w, float img_h, int normalize_inputs, int normalize_cameras,
+                           float* const* poses, float* const* rays, float* const* centers, int refine, int radius, double threshold,
+                           void* stream) {
+    clear_stale_hip_error();
+    return launch_decode_heatmaps_ex(heatmaps, dtype, batch_stride, batch, views, joints, height, width, post_process, center, scale,
+                                     pixels, conf, coords, cams_dev, img_w, img_h, normalize_inputs, normalize_cameras, poses, rays,
+                                     centers, refine, radius, threshold, (hipStream_t)stream);
+}
+
+int mpl_render_heatmaps(void* const* heatmaps, int dtype, long long batch_stride, int batch, int views, int joints, int height, int width,
+                        const float* pixels, const float* conf, const float* center, const float* scale, double stride_x,
+                        double stride_y, int mode, double sigma, double noise_level, uint64_t noise_key, long long first_index,
+                        float* weight, float* cells, void* stream) {
+    clear_stale_hip_error();
+    return launch_render_heatmaps(heatmaps, dtype, batch_stride, batch, views, joints, height, width, pixels, conf, center, scale,
+                                  stride_x, stride_y, mode, sigma, noise_level, noise_key, first_index, weight, cells,
+                                  (hipStream_t)stream);
+}
+
 size_t mpl_rpsm_workspace_bytes(int batch, int joints, int first_nbins) { return rpsm_workspace_bytes(batch, joints, first_nbins); }
 
 int mpl_rpsm(const void* const* heatmaps, int dtype, long long batch_stride, int batch, int views, int joints, int height, int width,

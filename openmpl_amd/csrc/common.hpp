@@ -330,6 +330,18 @@ int launch_decode_heatmaps(const void* const* heatmaps, int dtype, long long bat
                            const double* cams_dev, float img_w, float img_h, int norm_in, int norm_cam, float* const* poses,
                            float* const* rays, float* const* centers, hipStream_t s);
 
+// the same with the integer peak refined to a sub-pixel coordinate (mpl_decode_heatmaps_ex); refine == MPL_REFINE_NONE is the call above
+int launch_decode_heatmaps_ex(const void* const* heatmaps, int dtype, long long batch_stride, int B, int V, int J, int H, int W,
+                              int post_process, const float* center, const float* scale, float* pixels, float* conf, float* coords,
+                              const double* cams_dev, float img_w, float img_h, int norm_in, int norm_cam, float* const* poses,
+                              float* const* rays, float* const* centers, int refine, int radius, double threshold, hipStream_t s);
+
+// heatmap_render.hip: 2D joints -> heatmaps (mpl_render_heatmaps)
+int launch_render_heatmaps(void* const* heatmaps, int dtype, long long batch_stride, int B, int V, int J, int H, int W,
+                           const float* pixels, const float* conf, const float* center, const float* scale, double stride_x,
+                           double stride_y, int mode, double sigma, double noise_level, unsigned long long noise_key,
+                           long long first_index, float* weight, float* cells, hipStream_t s);
+
 // rpsm.hip: the recursive pictorial structure model on whole heatmaps (mpl_rpsm)
 size_t rpsm_workspace_bytes(int B, int J, int first_nbins);
 int launch_rpsm(const void* const* heatmaps, int dtype, long long batch_stride, int B, int V, int J, int H, int W, const float* center,

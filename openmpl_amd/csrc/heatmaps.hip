@@ -15,6 +15,12 @@
 // flags NaNs; a flagged lane (rare) looks up its first NaN.  Lanes and waves merge by one total order -- NaN above everything,
 // then the value (-0 == 0), then the lower index -- so the result is np.argmax's whatever the reduction tree, and both forms
 // and both paths give identical outputs.  No atomics, no scratch; 16-bit maps are widened exactly.
+//
+// Sub-pixel decoding (mpl_decode_heatmaps_ex) replaces the quarter-cell shift by a refinement of the integer peak, chosen by the
+// template parameter RF after the scan, which it does not touch: MPL_REFINE_GAUSSIAN, the log-quadratic fit through the peak and
+// its neighbours on each axis, on the finishing lane; MPL_REFINE_CENTROID, the thresholded window centroid that the reference's
+// find_tensor_peak_batch (inference.py:84-134) means to compute, spread over the finishing wave.  RF = MPL_REFINE_NONE compiles
+// to the kernels as they were.
 #include "common.hpp"
 #include "views.hpp"
 
@@ -32,6 +38,8 @@ struct DecodeParams : HeatmapTable {
     int post;
     double w, h;
     int norm_in, norm_cam;
+    int radius;                      // MPL_REFINE_CENTROID: the window is (2 radius + 1)^2 cells
+    double threshold;                // MPL_REFINE_CENTROID: values not above it count as 0
 };
 
 constexpr int DECODE_EMPTY = 0x7fffffff;     // index of a lane that has seen no value above -inf
@@ -95,7 +103,45 @@ __device__ __forceinline__ float hm_quarter(float hi, float lo) {      // 0.25 *
     return hi > lo ? 0.25f : (hi < lo ? -0.25f : 0.0f);
 }
 
-template <int DT, int WAVES>
+// ---- sub-pixel refinement of the integer peak (mpl_decode_heatmaps_ex), after the scan and the merge; RF is MPL_REFINE_*.
+
+// MPL_REFINE_GAUSSIAN, one axis: the log-quadratic fit through the peak f0 (l0 = ln f0) and its two neighbours `stride` elements
+// away; c is the peak's coordinate on the axis of n cells.  Exact for a Gaussian of any sigma; within +/-0.5 as f0 is the maximum.
+template <int DT>
+__device__ __forceinline__ double hm_log_quadratic(const char* base, size_t at, size_t stride, int c, int n, double l0) {
+    if (c == 0 || c == n - 1) return 0.0;
+    const float fm = hm_load<DT>(base, at - stride), fp = hm_load<DT>(base, at + stride);
+    if (!(fm > 0.0f && fm < INFINITY && fp > 0.0f && fp < INFINITY)) return 0.0;
+    const double a = l0 - log((double)fp), b = l0 - log((double)fm);
+    return a + b == 0.0 ? 0.0 : (b - a) / (2.0 * (a + b));
+}
+
+// MPL_REFINE_CENTROID: the thresholded centroid of the window about the peak (px, py), relative to the peak.  Called by all 64
+// lanes of the finishing wave with the same arguments: cell t = (j + r) * (2r + 1) + (i + r) goes to lane t % 64, a lane adds its
+// cells in increasing t, the lanes add up pairwise -- one order, whatever the form of the kernel.  Every lane returns the sums.
+template <int DT>
+__device__ __forceinline__ void hm_centroid(const char* base, int px, int py, int W, int H, int r, double threshold, int lane, double& dx,
+                                            double& dy) {
+    const int n = 2 * r + 1;
+    double sw = 0.0, sx = 0.0, sy = 0.0;
+    for (int t = lane; t < n * n; t += 64) {
+        const int i = t % n - r, j = t / n - r, x = px + i, y = py + j;
+        if (x < 0 || x >= W || y < 0 || y >= H) continue;
+        const double w = (double)hm_load<DT>(base, (size_t)y * W + x);
+        if (w > threshold) { sw += w; sx += w * (double)i; sy += w * (double)j; }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        sw += __shfl_xor(sw, off, 64);
+        sx += __shfl_xor(sx, off, 64);
+        sy += __shfl_xor(sy, off, 64);
+    }
+    const double S = sw + 2.22e-16;
+    dx = sx / S;
+    dy = sy / S;
+}
+
+template <int DT, int WAVES, int RF>
 __global__ __launch_bounds__(256) void decode_kernel(const DecodeParams p) {
     constexpr int NT = 64 * WAVES, E = HmElem<DT>::per_chunk, ES = HmElem<DT>::size;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -167,6 +213,10 @@ __global__ __launch_bounds__(256) void decode_kernel(const DecodeParams p) {
 #pragma unroll
     for (int i = 0; i < 16; ++i) c[i] = __shfl(cam, i, 64);
     const float box_x = __shfl(box, 0, 64), box_y = __shfl(box, 1, 64), box_s = __shfl(box, 2, 64);
+    double rdx = 0.0, rdy = 0.0;                                     // the refinement's offset, where it applies
+    if (RF == MPL_REFINE_CENTROID) {                                 // every lane holds the merged (cur, idx)
+        if (cur > 0.0f && cur < INFINITY) hm_centroid<DT>(base, idx % p.W, idx / p.W, p.W, p.H, p.radius, p.threshold, lane, rdx, rdy);
+    }
     if (lane != 0) return;
 
     if (idx == DECODE_EMPTY) idx = 0;                                // every value is -inf: np.argmax says 0
@@ -174,10 +224,20 @@ __global__ __launch_bounds__(256) void decode_kernel(const DecodeParams p) {
     const bool positive = maxval > 0.0f;
     const int px = positive ? idx % p.W : 0, py = positive ? idx / p.W : 0;
     float cx = (float)px, cy = (float)py;
-    if (p.post && 1 < px && px < p.W - 1 && 1 < py && py < p.H - 1) {
+    if (RF == MPL_REFINE_NONE && p.post && 1 < px && px < p.W - 1 && 1 < py && py < p.H - 1) {
         const size_t at = (size_t)py * p.W + px;
         cx += hm_quarter(hm_load<DT>(base, at + 1), hm_load<DT>(base, at - 1));
         cy += hm_quarter(hm_load<DT>(base, at + p.W), hm_load<DT>(base, at - p.W));
+    }
+    if (RF != MPL_REFINE_NONE && positive && maxval < INFINITY) {
+        if (RF == MPL_REFINE_GAUSSIAN) {
+            const size_t at = (size_t)py * p.W + px;
+            const double l0 = log((double)maxval);
+            rdx = hm_log_quadratic<DT>(base, at, 1, px, p.W, l0);
+            rdy = hm_log_quadratic<DT>(base, at, (size_t)p.W, py, p.H, l0);
+        }
+        cx = (float)((double)px + rdx);
+        cy = (float)((double)py + rdy);
     }
     if (p.coords) {
         p.coords[(size_t)m * 2] = cx;
@@ -200,21 +260,30 @@ __global__ __launch_bounds__(256) void decode_kernel(const DecodeParams p) {
     }
 }
 
-template <int DT>
+template <int DT, int RF>
 static void decode_launch(const DecodeParams& p, int waves, hipStream_t s) {
     if (waves == 4)
-        hipLaunchKernelGGL((decode_kernel<DT, 4>), dim3((unsigned)p.total), dim3(256), 0, s, p);
+        hipLaunchKernelGGL((decode_kernel<DT, 4, RF>), dim3((unsigned)p.total), dim3(256), 0, s, p);
     else
-        hipLaunchKernelGGL((decode_kernel<DT, 1>), dim3((unsigned)((p.total + 3) / 4)), dim3(256), 0, s, p);
+        hipLaunchKernelGGL((decode_kernel<DT, 1, RF>), dim3((unsigned)((p.total + 3) / 4)), dim3(256), 0, s, p);
 }
 
-int launch_decode_heatmaps(const void* const* heatmaps, int dtype, long long batch_stride, int B, int V, int J, int H, int W,
-                           int post_process, const float* center, const float* scale, float* pixels, float* conf, float* coords,
-                           const double* cams_dev, float img_w, float img_h, int norm_in, int norm_cam, float* const* poses,
-                           float* const* rays, float* const* centers, hipStream_t s) {
+template <int DT>
+static void decode_launch(const DecodeParams& p, int waves, int refine, hipStream_t s) {
+    if (refine == MPL_REFINE_GAUSSIAN) decode_launch<DT, MPL_REFINE_GAUSSIAN>(p, waves, s);
+    else if (refine == MPL_REFINE_CENTROID) decode_launch<DT, MPL_REFINE_CENTROID>(p, waves, s);
+    else decode_launch<DT, MPL_REFINE_NONE>(p, waves, s);
+}
+
+int launch_decode_heatmaps_ex(const void* const* heatmaps, int dtype, long long batch_stride, int B, int V, int J, int H, int W,
+                              int post_process, const float* center, const float* scale, float* pixels, float* conf, float* coords,
+                              const double* cams_dev, float img_w, float img_h, int norm_in, int norm_cam, float* const* poses,
+                              float* const* rays, float* const* centers, int refine, int radius, double threshold, hipStream_t s) {
     if (!pixels || !conf || B <= 0 || V <= 0 || J <= 0 || H <= 0 || W <= 0) return MPL_E_INVALID;
     if ((center != nullptr) != (scale != nullptr)) return MPL_E_INVALID;
     if (cams_dev && (!poses || !rays || !centers || !(img_w > 0) || !(img_h > 0))) return MPL_E_INVALID;
+    if (refine < MPL_REFINE_NONE || refine > MPL_REFINE_CENTROID || (refine != MPL_REFINE_NONE && post_process)) return MPL_E_INVALID;
+    if (refine == MPL_REFINE_CENTROID && (radius < 1 || radius > 8 || threshold != threshold)) return MPL_E_INVALID;
     DecodeParams p;
     if (const int rc = heatmap_table_fill(p, heatmaps, dtype, batch_stride, B, V, J, H, W)) return rc;
     if ((long long)B * V * J > (1ll << 30)) return MPL_E_UNSUPPORTED;
@@ -222,12 +291,21 @@ int launch_decode_heatmaps(const void* const* heatmaps, int dtype, long long bat
     p.center = center; p.scale = scale; p.cams = cams_dev; p.pixels = pixels; p.conf = conf; p.coords = coords;
     p.total = B * V * J; p.post = post_process;
     p.w = img_w; p.h = img_h; p.norm_in = norm_in; p.norm_cam = norm_cam;
+    p.radius = refine == MPL_REFINE_CENTROID ? radius : 0; p.threshold = refine == MPL_REFINE_CENTROID ? threshold : 0.0;
     const int waves = decode_waves_per_map((size_t)H * W * (dtype == MPL_HM_F32 ? 4 : 2));
     ProfScope prof(MPL_K_FUSE_HEAD, s);
-    if (dtype == MPL_HM_F32) decode_launch<MPL_HM_F32>(p, waves, s);
-    else if (dtype == MPL_HM_F16) decode_launch<MPL_HM_F16>(p, waves, s);
-    else decode_launch<MPL_HM_BF16>(p, waves, s);
+    if (dtype == MPL_HM_F32) decode_launch<MPL_HM_F32>(p, waves, refine, s);
+    else if (dtype == MPL_HM_F16) decode_launch<MPL_HM_F16>(p, waves, refine, s);
+    else decode_launch<MPL_HM_BF16>(p, waves, refine, s);
     return hip_check_launch();
+}
+
+int launch_decode_heatmaps(const void* const* heatmaps, int dtype, long long batch_stride, int B, int V, int J, int H, int W,
+                           int post_process, const float* center, const float* scale, float* pixels, float* conf, float* coords,
+                           const double* cams_dev, float img_w, float img_h, int norm_in, int norm_cam, float* const* poses,
+                           float* const* rays, float* const* centers, hipStream_t s) {
+    return launch_decode_heatmaps_ex(heatmaps, dtype, batch_stride, B, V, J, H, W, post_process, center, scale, pixels, conf, coords,
+                                     cams_dev, img_w, img_h, norm_in, norm_cam, poses, rays, centers, MPL_REFINE_NONE, 0, 0.0, s);
 }
 
 }  // namespace mpl

@@ -8,7 +8,7 @@
 // to the fp64 pixel.  One work item per (pose, view, joint), one launch, no LDS, no atomics, nothing depends on the launch
 // geometry.  Arithmetic is fp64 on the fp32 tensors and every output is rounded once.
 //
-// Random numbers are the counter-based SplitMix64 draws of openmpl_amd/detrng.py: draw(key, i) = mix(key + (i + 1) * GOLD), top
+// Random numbers are the counter-based SplitMix64 draws of openmpl_amd/detrng.py (detrng.hpp): draw(key, i) = mix(key + (i + 1) * GOLD), top
 // 53 bits -> [0,1).  The keys come from the host (detrng._stream_key); per-pose streams are indexed by first_index + b, per-joint
 // streams by ((first_index + b) * V + v) * J + j, so a run cut into batches draws the values of the uncut run, and every (v, j)
 // item of a pose recomputes the pose's rotation and translation from the same counter.
@@ -16,6 +16,7 @@
 // The one deviation: a joint at z_cam <= 1e-9 (the reference divides anyway) gets confidence 0 and pixel (0,0) and skips the
 // noise, visibility and missing-joint steps; its ray and normalised pose follow from that pixel.
 #include "common.hpp"
+#include "detrng.hpp"
 #include "views.hpp"
 
 namespace mpl {
@@ -38,17 +39,6 @@ struct SynthParams {
     int B, V, J;
 };
 
-__device__ __forceinline__ unsigned long long synth_mix(unsigned long long z) {
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
-// detrng.uniform01: element i of the stream `key`, a double in [0,1) with 53 bits
-__device__ __forceinline__ double synth_draw(unsigned long long key, unsigned long long i) {
-    return (double)(synth_mix(key + (i + 1ull) * 0x9E3779B97F4A7C15ull) >> 11) * (1.0 / 9007199254740992.0);
-}
-
 __global__ __launch_bounds__(256) void synthesize_views_kernel(const SynthParams p) {
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     const long long total = (long long)p.B * p.V * p.J;
@@ -63,7 +53,7 @@ __global__ __launch_bounds__(256) void synthesize_views_kernel(const SynthParams
     const float* xi = p.x3d + ((size_t)b * p.J + j) * 3;
     double X = xi[0], Y = xi[1], Z = xi[2];
     if (p.rot_deg || o.rotate) {
-        const double deg = p.rot_deg ? (double)p.rot_deg[b] : synth_draw(o.key_rot, gpose) * 360.0;
+        const double deg = p.rot_deg ? (double)p.rot_deg[b] : detrng_draw(o.key_rot, gpose) * 360.0;
         const double a = deg * (3.141592653589793 / 180.0);
         const double ca = cos(a), sa = sin(a);
         const double x0 = X, y0 = Y;
@@ -75,8 +65,8 @@ __global__ __launch_bounds__(256) void synthesize_views_kernel(const SynthParams
         Y += (double)p.trans[(size_t)b * 3 + 1];
         Z += (double)p.trans[(size_t)b * 3 + 2];
     } else if (o.room) {
-        X += synth_draw(o.key_room_x, gpose) * (o.room_max_x - o.room_min_x) + o.room_min_x;
-        Y += synth_draw(o.key_room_y, gpose) * (o.room_max_y - o.room_min_y) + o.room_min_y;
+        X += detrng_draw(o.key_room_x, gpose) * (o.room_max_x - o.room_min_x) + o.room_min_x;
+        Y += detrng_draw(o.key_room_y, gpose) * (o.room_max_y - o.room_min_y) + o.room_min_y;
     }
 
     // 2. projection: x_cam = R (X - t), px = (fx x / z + cx, fy y / z + cy)
@@ -105,7 +95,7 @@ __global__ __launch_bounds__(256) void synthesize_views_kernel(const SynthParams
                 n0 = p.noise[(size_t)idx * 2];
                 n1 = p.noise[(size_t)idx * 2 + 1];
             } else {   // Box-Muller
-                const double u1 = 1.0 - synth_draw(o.key_noise0, gitem), u2 = synth_draw(o.key_noise1, gitem);
+                const double u1 = 1.0 - detrng_draw(o.key_noise0, gitem), u2 = detrng_draw(o.key_noise1, gitem);
                 const double r = sqrt(-2.0 * log(u1)), t = 6.283185307179586 * u2;
                 n0 = r * cos(t);
                 n1 = r * sin(t);
@@ -133,7 +123,7 @@ __global__ __launch_bounds__(256) void synthesize_views_kernel(const SynthParams
         }
         // 5. missing joints
         if (o.missing_level > 0.0) {
-            const double u = p.miss_u ? (double)p.miss_u[idx] : synth_draw(o.key_missing, gitem);
+            const double u = p.miss_u ? (double)p.miss_u[idx] : detrng_draw(o.key_missing, gitem);
             if (u < o.missing_level) { cf *= 0.0; x *= 0.0; y *= 0.0; }
         }
     }

@@ -1,5 +1,6 @@
 // The three data formats of the pose utilities, each stated once: the camera record, the model-input lists and the heatmap table.
-// inputs.hip, heatmaps.hip, synth.hip and rpsm.hip read and write them through this header only.
+// inputs.hip, heatmaps.hip, heatmap_render.hip, synth.hip and rpsm.hip read and write them through this header only (DESIGN.md
+// section 7).
 #pragma once
 #include "common.hpp"
 
@@ -90,6 +91,25 @@ __device__ __forceinline__ float hm_fetch(const void* base, size_t i, int dt) {
     if (dt == MPL_HM_F32) return static_cast<const float*>(base)[i];
     const unsigned u = static_cast<const unsigned short*>(base)[i];
     return dt == MPL_HM_BF16 ? hm_widen16<MPL_HM_BF16>(u) : hm_widen16<MPL_HM_F16>(u);
+}
+
+// The way back, for the kernel that writes maps: an fp64 value rounded ONCE (to nearest, ties to even) to dtype DT, denormals
+// kept.  fp32 is the hardware conversion.  A 16-bit type goes through an fp32 that is rounded to odd -- truncated towards zero with
+// the last bit set when anything was lost -- which has 13 (fp16) or 16 (bf16) bits more than the target, so the second rounding
+// sees on which side of every tie the fp64 value lay.
+template <int DT>
+__device__ __forceinline__ unsigned hm_narrow(double x) {
+    float f = (float)x;
+    if (DT == MPL_HM_F32) return __float_as_uint(f);
+    unsigned u = __float_as_uint(f);
+    if ((double)f != x && x == x && (u & 0x7f800000u) != 0x7f800000u) {      // inexact, and neither NaN nor overflowed
+        if (fabs((double)f) > fabs(x)) u -= 1;                               // the magnitude below: towards zero
+        u |= 1;
+        f = __uint_as_float(u);
+    }
+    if (DT == MPL_HM_F16) return (unsigned)__builtin_bit_cast(unsigned short, (_Float16)f);
+    if (f != f) return 0x7fc0u | (u >> 31 << 15);
+    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
 }
 
 struct HeatmapTable {
