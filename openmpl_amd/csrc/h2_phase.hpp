@@ -1,6 +1,8 @@
 // Device side of the packed-operand GEMM engines of the FPT block stack (h2_gemm.hip: fp32 arithmetic from two fp16 parts,
-// NP = 2; b1_gemm.hip: bf16 operands, NP = 1): tile constants, the GEMM phase (h2_phase), the one-GEMM kernel and the two
-// persistent stack kernels, as templates that each engine's translation unit instantiates for its own NP.
+// NP = 2; b1_gemm.hip: bf16 operands, NP = 1): tile constants, the GEMM phase (h2_phase), the one-GEMM kernel and the four
+// persistent stack kernels, as templates that each engine's translation unit instantiates for its own NP -- h2_stack2_kernel (pairs of
+// row tiles) here, the three one-tile walkers h2_stack_kernel / h2_stackn_kernel / h2_stackd_kernel as three inclusions of ONE body,
+// h2_stack_walk.inc -- and the launcher of a stack with the rule that picks the kernel (h2_stack_form, h2_launch_stack).
 #pragma once
 #include <mutex>
 #include <type_traits>
@@ -1543,6 +1545,17 @@ __device__ __forceinline__ bool h2_phase(const H2Args& a, char* smem, int tid, i
     return true;
 }
 
+// The three wave roles of a workgroup, written once: the waves 0..3 run the slots 0 .. H2_T0 - 1 of a tile with WCS##0 W pieces per
+// stage, the waves 4, 5 and 6, 7 the slots from H2_T0 on with WCS##1 / WCS##2 (WCS = H2_WC: one row tile per stage, H2_R2_WC: two).
+// PH(NTW, WC, SLOT0, ...) is the h2_phase call of one role as the site writes it (chain flag, RT, trailing arguments).  W47: the
+// waves 4..7 are ONE role (direct-W form); as a constant it keeps the third branch out of the kernel.
+#define H2_BY_ROLE(wv, W47, WCS, PH, ...)                                               \
+    do {                                                                                \
+        if ((wv) < 4) { PH(H2_T0, WCS##0, 0, __VA_ARGS__); }                            \
+        else if ((W47) || (wv) < 6) { PH(NT - H2_T0, WCS##1, H2_T0, __VA_ARGS__); }     \
+        else { PH(NT - H2_T0, WCS##2, H2_T0, __VA_ARGS__); }                            \
+    } while (0)
+
 template <int EPI, bool LNF, int NPASS, int NP = 2>
 __global__ __launch_bounds__(512, 2) void h2_gemm_kernel(const H2Args a) {
     extern __shared__ __attribute__((aligned(1024))) char smem[];
@@ -1561,9 +1574,9 @@ __global__ __launch_bounds__(512, 2) void h2_gemm_kernel(const H2Args a) {
             tn = b / a.grid_m;
         }
     }
-    if (wave < 4) h2_phase<EPI, LNF, NPASS, H2_T0, false, H2_WC0, 1, NP>(a, smem, tid, wave, 0, tm, tn, nullptr, 0u);
-    else if (wave < 6) h2_phase<EPI, LNF, NPASS, NT - H2_T0, false, H2_WC1, 1, NP>(a, smem, tid, wave, H2_T0, tm, tn, nullptr, 0u);
-    else h2_phase<EPI, LNF, NPASS, NT - H2_T0, false, H2_WC2, 1, NP>(a, smem, tid, wave, H2_T0, tm, tn, nullptr, 0u);
+#define H2_GEMM_PHASE(NTW, WC, SLOT0, CHAIN) h2_phase<EPI, LNF, NPASS, NTW, CHAIN, WC, 1, NP>(a, smem, tid, wave, SLOT0, tm, tn, nullptr, 0u)
+    H2_BY_ROLE(wave, false, H2_WC, H2_GEMM_PHASE, false);
+#undef H2_GEMM_PHASE
 }
 
 // ---------------------------------------------------------------------------------------------- whole block stack
@@ -1642,7 +1655,8 @@ __device__ __forceinline__ int h2_team_on_one_xcd(const H2StackArgs& s, int team
     return (s.plain_ok && m != 0u && (m & (m - 1u)) == 0u) ? 1 : 0;
 }
 
-// a phase of h2_stack_kernel: the whole-tile chain form with the cross-phase W prefetch
+// a phase of h2_stack_kernel: the whole-tile chain form with the cross-phase W prefetch.  (The wrapper is an inline level the kernel
+// was tuned with: calling h2_phase directly gives other gfx950 code, HISTORY.md)
 template <int EPI, bool LNF, int NPASS, int NTW, int WC, int NP>
 __device__ __forceinline__ bool h2_phase_pf(const H2Args& a, char* smem, int tid, int wave, int slot0, int tm, int tn,
                                             unsigned* chain, unsigned chain_need, H2Pf& pf) {
@@ -1650,88 +1664,12 @@ __device__ __forceinline__ bool h2_phase_pf(const H2Args& a, char* smem, int tid
                                                                               true, 0, 4, &pf);
 }
 
-template <int NP>
-__global__ __launch_bounds__(512, 2) void h2_stack_kernel(const H2StackArgs s) {
-    extern __shared__ __attribute__((aligned(1024))) char smem[];
-    const int tid = threadIdx.x;
-    const int wave_s = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int G = s.G, D = s.D;
-    int team, tn;
-    {
-        const int b = blockIdx.x;
-        team = (b & 7) + 8 * ((b >> 3) / G);
-        tn = (b >> 3) % G;
-        if (team >= s.n_teams) return;
-    }
-    if (tid == 0) *reinterpret_cast<volatile unsigned*>(smem + H2_FAIL) = 0u;
-    h2_publish_xcd(s, team, tid);
-    int plain = 0, seen = 0;       // plain hand-off stores once the team is known to sit on one XCD (h2_publish_xcd)
-    __syncthreads();
-    H2Pf pf{0u, 0, nullptr, 0u, 1};      // cross-phase W prefetch: the first phase of the launch fills its own ring
-    for (int tile0 = team; tile0 < s.n_tiles; tile0 += s.n_teams) {
-        unsigned need = 0;
-        for (int ph = 0; ph < s.n_phases; ++ph, need += G) {
-            if (!seen && ph >= 2) {       // the proj phase has seen every partner arrive: the team's placement word is complete
-                plain = __builtin_amdgcn_readfirstlane(h2_team_on_one_xcd(s, team));
-                seen = 1;
-            }
-            // the thread id is rebuilt from the wave index (a scalar) and the lane number every phase: kept in a register
-            // across the phases it was the one value the 256-register budget spilled to scratch
-            int wvp = wave_s, tile = tile0, tnp = tn;
-            asm volatile("" : "+s"(wvp), "+s"(tile), "+s"(tnp));
-            int tidp = wvp * 64 + (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-            asm volatile("" : "+v"(tidp));
-            const int wv = wvp;
-            unsigned* ctr = s.counters + tile;
-            const char* const* w = s.w[ph >> 2];
-            bool ok = true;
-            if (s.inject > 0 && ph == s.inject && tile == 0 && tnp == 0) return;     // fault injection (test hook)
-            // the W stream the phase behind this one starts with (H2Pf): the next phase of this tile, or the first phase of the
-            // team's next tile; nothing behind the last phase of the launch
-            {
-                int nph = ph + 1;
-                if (nph == s.n_phases) nph = tile0 + s.n_teams < s.n_tiles ? 0 : -1;
-                pf.nw = nullptr;
-                if (nph >= 0) {
-                    const int kind = nph & 3;
-                    const int npass = kind == 0 ? 3 : (kind == 2 ? 2 : 1);
-                    const int ktn = h2_ksteps(kind == 3 ? 2 * D : D, NP);
-                    if (npass * ktn >= H2_PF_MIN_T) {
-                        // column group of pass g: g G + tn (qkv), 2 tn + g (fc1), tn (proj, fc2) -- h2_phase's colbase / BN
-                        pf.nw = s.w[nph >> 2][kind] + (size_t)(npass == 3 ? tnp : npass * tnp) * ktn * H2_W;
-                        pf.pstride = (unsigned)((npass == 3 ? G : 1) * ktn * H2_W);
-                        pf.npass = npass;
-                    }
-                }
-            }
-            switch (ph & 3) {
-                case 0: {   // x = x + proj(attn(qkv(norm1(x))))   (Block.forward :84-90)
-                    H2Args a = h2_args_qkv<NP>(s, w[0], D, G, plain);
-                    if (wv < 4) ok = h2_phase_pf<H2_EPI_ATT, true, 3, H2_T0, H2_WC0, NP>(a, smem, tidp, wv, 0, tile, tnp, ctr, need, pf);
-                    else if (wv < 6) ok = h2_phase_pf<H2_EPI_ATT, true, 3, NT - H2_T0, H2_WC1, NP>(a, smem, tidp, wv, H2_T0, tile, tnp, ctr, need, pf);
-                    else ok = h2_phase_pf<H2_EPI_ATT, true, 3, NT - H2_T0, H2_WC2, NP>(a, smem, tidp, wv, H2_T0, tile, tnp, ctr, need, pf);
-                    break;
-                }
-                case 2: {   // x = x + fc2(gelu(fc1(norm2(x))))    (Block.forward :91, Mlp.forward :31-37)
-                    H2Args a = h2_args_fc1<NP>(s, w[2], D, G, plain);
-                    if (wv < 4) ok = h2_phase_pf<H2_EPI_GELU, true, 2, H2_T0, H2_WC0, NP>(a, smem, tidp, wv, 0, tile, tnp, ctr, need, pf);
-                    else if (wv < 6) ok = h2_phase_pf<H2_EPI_GELU, true, 2, NT - H2_T0, H2_WC1, NP>(a, smem, tidp, wv, H2_T0, tile, tnp, ctr, need, pf);
-                    else ok = h2_phase_pf<H2_EPI_GELU, true, 2, NT - H2_T0, H2_WC2, NP>(a, smem, tidp, wv, H2_T0, tile, tnp, ctr, need, pf);
-                    break;
-                }
-                default: {
-                    const bool fc2 = (ph & 3) == 3;
-                    H2Args a = h2_args_res<NP>(s, fc2 ? w[3] : w[1], fc2, D, G, plain);
-                    if (wv < 4) ok = h2_phase_pf<H2_EPI_RES, false, 1, H2_T0, H2_WC0, NP>(a, smem, tidp, wv, 0, tile, tnp, ctr, need, pf);
-                    else if (wv < 6) ok = h2_phase_pf<H2_EPI_RES, false, 1, NT - H2_T0, H2_WC1, NP>(a, smem, tidp, wv, H2_T0, tile, tnp, ctr, need, pf);
-                    else ok = h2_phase_pf<H2_EPI_RES, false, 1, NT - H2_T0, H2_WC2, NP>(a, smem, tidp, wv, H2_T0, tile, tnp, ctr, need, pf);
-                    break;
-                }
-            }
-            if (!ok) return;
-        }
-    }
-}
+// The three one-tile stack kernels are ONE body (h2_stack_walk.inc), instantiated under their names by the form it walks.
+// Form 0, whole tiles: a team walks one 64-row tile per step, every phase entered with the W pieces of its first stages already in
+// the ring (h2_phase PF, H2Pf: the cross-phase W prefetch).
+#define H2_WALK_KERNEL h2_stack_kernel
+#define H2_WALK_FORM 0
+#include "h2_stack_walk.inc"
 
 // The same stack for teams that own TWO OR MORE row tiles (M > 64 x the number of teams the chip holds: the FULL flag set at
 // B = 1024, eight views, B >= 2048): a team walks PAIRS of row tiles.  proj, fc1 and fc2 run the two-tile stage (h2_phase RT = 2:
@@ -1756,9 +1694,6 @@ __global__ __launch_bounds__(512, 2) void h2_stack2_kernel(const H2StackArgs s) 
     h2_publish_xcd(s, team, tid);
     int plain = 0, seen = 0;       // plain hand-off stores once the team is known to sit on one XCD (h2_publish_xcd)
     __syncthreads();
-    auto vecs = [&](const char* w2, int N, int K) -> const float* {
-        return reinterpret_cast<const float*>(w2 + (size_t)(N / BN) * (K / BK) * H2_W);
-    };
     const int n_pairs = (s.n_tiles + 1) >> 1;
     for (int pair0 = team; pair0 < n_pairs; pair0 += s.n_teams) {
         unsigned need = 0;
@@ -1787,35 +1722,33 @@ __global__ __launch_bounds__(512, 2) void h2_stack2_kernel(const H2StackArgs s) 
             const char* const* w = s.w[app];
             bool ok = true;
             if (s.inject > 0 && ph == s.inject && !second && pair == 0 && tnp == 0) return;     // fault injection (test hook)
+// one role of a step: RT row tiles per stage, (pair of) row tile(s) tm, column group tn
+#define H2_STEP(NTW, WC, SLOT0, EPI, LNF, NPASS, RT, tm, tn) \
+    ok = h2_phase<EPI, LNF, NPASS, NTW, true, WC, RT>(a, smem, tidp, wv, SLOT0, tm, tn, ctr, nd, arr)
             if (k < 2) {   // x = x + proj(attn(qkv(norm1(x)))): one row tile at a time
-                const float* v = vecs(w[0], 3 * D, D);
+                const float* v = h2_trailer<NP>(w[0], 3 * D, D);
                 const H2Args a{nullptr, s.x, D, w[0], v, v + 3 * D, s.stats, nullptr, v + 12 * D, nullptr, 0, nullptr, 0, s.att2,
                                nullptr, s.M, 3 * D, D, s.rpt, s.n_tiles, G, s.eps, s.n_tok, D / s.heads, s.dbg, s.err_ws, s.err_host,
                                s.spin_log2, plain};
                 const int tile = 2 * pair + k;
-                if (wv < 4) ok = h2_phase<H2_EPI_ATT, true, 3, H2_T0, true, H2_WC0>(a, smem, tidp, wv, 0, tile, tnp, ctr, nd, arr);
-                else if (wv < 6) ok = h2_phase<H2_EPI_ATT, true, 3, NT - H2_T0, true, H2_WC1>(a, smem, tidp, wv, H2_T0, tile, tnp, ctr, nd, arr);
-                else ok = h2_phase<H2_EPI_ATT, true, 3, NT - H2_T0, true, H2_WC2>(a, smem, tidp, wv, H2_T0, tile, tnp, ctr, nd, arr);
+                H2_BY_ROLE(wv, false, H2_WC, H2_STEP, H2_EPI_ATT, true, 3, 1, tile, tnp);
             } else if (k == 3 || k == 4) {   // fc1 + GELU: the workgroup's two column groups one after the other (two accumulator sets
                                              // for two row tiles do not fit the register file beside the double-buffered fragments)
-                const float* v = vecs(w[2], 2 * D, D);
+                const float* v = h2_trailer<NP>(w[2], 2 * D, D);
                 const H2Args a{nullptr, s.x, D, w[2], v, v + 2 * D, s.stats, nullptr, v + 8 * D, nullptr, 0, nullptr, 0, s.hid2,
                                nullptr, s.M, 2 * D, D, s.rpt, s.n_tiles, G, s.eps, 0, 0, s.dbg, s.err_ws, s.err_host, s.spin_log2, plain};
                 const int cg = 2 * tnp + (k - 3);
-                if (wv < 4) ok = h2_phase<H2_EPI_GELU, true, 1, H2_T0, true, H2_R2_WC0, 2>(a, smem, tidp, wv, 0, pair, cg, ctr, nd, arr);
-                else if (wv < 6) ok = h2_phase<H2_EPI_GELU, true, 1, NT - H2_T0, true, H2_R2_WC1, 2>(a, smem, tidp, wv, H2_T0, pair, cg, ctr, nd, arr);
-                else ok = h2_phase<H2_EPI_GELU, true, 1, NT - H2_T0, true, H2_R2_WC2, 2>(a, smem, tidp, wv, H2_T0, pair, cg, ctr, nd, arr);
+                H2_BY_ROLE(wv, false, H2_R2_WC, H2_STEP, H2_EPI_GELU, true, 1, 2, pair, cg);
             } else {  // proj (A = attention output, K = D) and fc2 (A = hidden, K = 2D)
                 const bool fc2 = k == 5;
                 const int K = fc2 ? 2 * D : D;
                 const char* w2 = fc2 ? w[3] : w[1];
-                const float* v = vecs(w2, D, K);
+                const float* v = h2_trailer<NP>(w2, D, K);
                 const H2Args a{fc2 ? s.hid2 : s.att2, nullptr, 0, w2, v, v + D, nullptr, nullptr, nullptr, s.x, D, s.x, D, nullptr, s.stats,
                                s.M, D, K, s.rpt, s.n_tiles, G, s.eps, 0, 0, s.dbg, s.err_ws, s.err_host, s.spin_log2, plain};
-                if (wv < 4) ok = h2_phase<H2_EPI_RES, false, 1, H2_T0, true, H2_R2_WC0, 2>(a, smem, tidp, wv, 0, pair, tnp, ctr, nd, arr);
-                else if (wv < 6) ok = h2_phase<H2_EPI_RES, false, 1, NT - H2_T0, true, H2_R2_WC1, 2>(a, smem, tidp, wv, H2_T0, pair, tnp, ctr, nd, arr);
-                else ok = h2_phase<H2_EPI_RES, false, 1, NT - H2_T0, true, H2_R2_WC2, 2>(a, smem, tidp, wv, H2_T0, pair, tnp, ctr, nd, arr);
+                H2_BY_ROLE(wv, false, H2_R2_WC, H2_STEP, H2_EPI_RES, false, 1, 2, pair, tnp);
             }
+#undef H2_STEP
             if (!ok) return;
             if (arr) need += G;
         }
@@ -1832,75 +1765,9 @@ __global__ __launch_bounds__(512, 2) void h2_stack2_kernel(const H2StackArgs s) 
 // Measured and dropped (round 5, tools/ab.sh): in the 16-row form seven waves wait ~450 cycles per stage at the barrier for the one
 // wave pair that multiplies (tools/chain_phase.py), so its W pieces were given to the six loader-only waves (three each, by
 // rank): no gain for the stage, and the extra instantiations cost every form of this kernel 8 % (SGPR spills 492 -> 768).
-template <int NP>
-__global__ __launch_bounds__(512, 2) void h2_stackn_kernel(const H2StackArgs s) {
-    extern __shared__ __attribute__((aligned(1024))) char smem[];
-    const int tid = threadIdx.x;
-    const int wave_s = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int G = s.G, D = s.D;
-    int team, tn;
-    {
-        const int b = blockIdx.x;
-        team = (b & 7) + 8 * ((b >> 3) / G);
-        tn = (b >> 3) % G;
-        if (team >= s.n_teams) return;
-    }
-    if (tid == 0) *reinterpret_cast<volatile unsigned*>(smem + H2_FAIL) = 0u;
-    h2_publish_xcd(s, team, tid);
-    int plain = 0, seen = 0;       // plain hand-off stores once the team is known to sit on one XCD (h2_publish_xcd)
-    __syncthreads();
-    const int rs = 4 / s.rgs;                    // sub-tiles per row tile
-    const int n_units = s.n_tiles * rs;
-    for (int unit0 = team; unit0 < n_units; unit0 += s.n_teams) {
-        unsigned need = 0;
-        for (int ph = 0; ph < s.n_phases; ++ph, need += G) {
-            if (!seen && ph >= 2) {       // the proj phase has seen every partner arrive: the team's placement word is complete
-                plain = __builtin_amdgcn_readfirstlane(h2_team_on_one_xcd(s, team));
-                seen = 1;
-            }
-            int wvp = wave_s, unit = unit0, tnp = tn;
-            asm volatile("" : "+s"(wvp), "+s"(unit), "+s"(tnp));
-            int tidp = wvp * 64 + (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-            asm volatile("" : "+v"(tidp));
-            const int wv = wvp;
-            const int tile = unit / rs, rg_lo = (unit - tile * rs) * s.rgs;
-            const bool act = (wv & 3) >= rg_lo && (wv & 3) < rg_lo + s.rgs;
-            unsigned* ctr = s.counters + H2_CTR_PER_TILE * tile + rg_lo;      // one arrival counter per sub-tile
-            const char* const* w = s.w[ph >> 2];
-            bool ok = true;
-            if (s.inject > 0 && ph == s.inject && unit == 0 && tnp == 0) return;     // fault injection (test hook)
-#define H2N_PHASE(EPI, LNF, NPASS)                                                                                                          \
-    do {                                                                                                                                    \
-        if (wv < 4) ok = act ? h2_phase<EPI, LNF, NPASS, H2_T0, true, H2_WC0, 1, NP, true>(a, smem, tidp, wv, 0, tile, tnp, ctr, need, true, rg_lo, s.rgs)   \
-                             : h2_phase<EPI, LNF, NPASS, H2_T0, true, H2_WC0, 1, NP, false>(a, smem, tidp, wv, 0, tile, tnp, ctr, need, true, rg_lo, s.rgs); \
-        else if (wv < 6) ok = act ? h2_phase<EPI, LNF, NPASS, NT - H2_T0, true, H2_WC1, 1, NP, true>(a, smem, tidp, wv, H2_T0, tile, tnp, ctr, need, true, rg_lo, s.rgs)   \
-                                  : h2_phase<EPI, LNF, NPASS, NT - H2_T0, true, H2_WC1, 1, NP, false>(a, smem, tidp, wv, H2_T0, tile, tnp, ctr, need, true, rg_lo, s.rgs); \
-        else ok = act ? h2_phase<EPI, LNF, NPASS, NT - H2_T0, true, H2_WC2, 1, NP, true>(a, smem, tidp, wv, H2_T0, tile, tnp, ctr, need, true, rg_lo, s.rgs)   \
-                      : h2_phase<EPI, LNF, NPASS, NT - H2_T0, true, H2_WC2, 1, NP, false>(a, smem, tidp, wv, H2_T0, tile, tnp, ctr, need, true, rg_lo, s.rgs); \
-    } while (0)
-            switch (ph & 3) {
-                case 0: {
-                    H2Args a = h2_args_qkv<NP>(s, w[0], D, G, plain);
-                    H2N_PHASE(H2_EPI_ATT, true, 3);
-                    break;
-                }
-                case 2: {
-                    H2Args a = h2_args_fc1<NP>(s, w[2], D, G, plain);
-                    H2N_PHASE(H2_EPI_GELU, true, 2);
-                    break;
-                }
-                default: {
-                    const bool fc2 = (ph & 3) == 3;
-                    H2Args a = h2_args_res<NP>(s, fc2 ? w[3] : w[1], fc2, D, G, plain);
-                    H2N_PHASE(H2_EPI_RES, false, 1);
-                    break;
-                }
-            }
-#undef H2N_PHASE
-            if (!ok) return;
-        }
-    }
-}
+#define H2_WALK_KERNEL h2_stackn_kernel
+#define H2_WALK_FORM 1
+#include "h2_stack_walk.inc"
 
 // Direct-W form of the 16-row teams (h2d_gemm.hip).  With 16 rows a stage of the ring form is bound by the serial chain of the
 // one wave pair that multiplies -- fragment reads, its DMA requests, a barrier per two stages, both waves on ONE SIMD -- while six
@@ -1908,72 +1775,9 @@ __global__ __launch_bounds__(512, 2) void h2_stackn_kernel(const H2StackArgs s) 
 // 4 + (rg_lo + 2) % 4), take their W fragments straight from L2 into a register ring and run the k loop without barriers; all
 // eight waves bring the A operand of the 16 rows into LDS once per phase.  Fragments, product order and epilogue are those of the
 // ring form: bitwise the same poses.
-template <int NP>
-__global__ __launch_bounds__(512, 2) void h2_stackd_kernel(const H2StackArgs s) {
-    extern __shared__ __attribute__((aligned(1024))) char smem[];
-    const int tid = threadIdx.x;
-    const int wave_s = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int G = s.G, D = s.D;
-    int team, tn;
-    {
-        const int b = blockIdx.x;
-        team = (b & 7) + 8 * ((b >> 3) / G);
-        tn = (b >> 3) % G;
-        if (team >= s.n_teams) return;
-    }
-    if (tid == 0) *reinterpret_cast<volatile unsigned*>(smem + H2_FAIL) = 0u;
-    h2_publish_xcd(s, team, tid);
-    int plain = 0, seen = 0;
-    __syncthreads();
-    const int n_units = s.n_tiles * 4;
-    for (int unit0 = team; unit0 < n_units; unit0 += s.n_teams) {
-        unsigned need = 0;
-        for (int ph = 0; ph < s.n_phases; ++ph, need += G) {
-            if (!seen && ph >= 2) {
-                plain = __builtin_amdgcn_readfirstlane(h2_team_on_one_xcd(s, team));
-                seen = 1;
-            }
-            int wvp = wave_s, unit = unit0, tnp = tn;
-            asm volatile("" : "+s"(wvp), "+s"(unit), "+s"(tnp));
-            int tidp = wvp * 64 + (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-            asm volatile("" : "+v"(tidp));
-            const int wv = wvp;
-            const int tile = unit >> 2, rg_lo = unit & 3;
-            const bool act = wv < 4 ? wv == rg_lo : (wv & 3) == ((rg_lo + 2) & 3);
-            unsigned* ctr = s.counters + H2_CTR_PER_TILE * tile + rg_lo;
-            const char* const* w = s.w[ph >> 2];
-            bool ok = true;
-            if (s.inject > 0 && ph == s.inject && unit == 0 && tnp == 0) return;     // fault injection (test hook)
-#define H2D_PHASE(EPI, LNF, NPASS)                                                                                                          \
-    do {                                                                                                                                    \
-        if (wv < 4) ok = act ? h2_phase<EPI, LNF, NPASS, H2_T0, true, H2_WC0, 1, NP, true, true>(a, smem, tidp, wv, 0, tile, tnp, ctr, need, true, rg_lo, 1)   \
-                             : h2_phase<EPI, LNF, NPASS, H2_T0, true, H2_WC0, 1, NP, false, true>(a, smem, tidp, wv, 0, tile, tnp, ctr, need, true, rg_lo, 1); \
-        else ok = act ? h2_phase<EPI, LNF, NPASS, NT - H2_T0, true, H2_WC1, 1, NP, true, true>(a, smem, tidp, wv, H2_T0, tile, tnp, ctr, need, true, rg_lo, 1)   \
-                      : h2_phase<EPI, LNF, NPASS, NT - H2_T0, true, H2_WC1, 1, NP, false, true>(a, smem, tidp, wv, H2_T0, tile, tnp, ctr, need, true, rg_lo, 1); \
-    } while (0)
-            switch (ph & 3) {
-                case 0: {
-                    H2Args a = h2_args_qkv<NP>(s, w[0], D, G, plain);
-                    H2D_PHASE(H2_EPI_ATT, true, 3);
-                    break;
-                }
-                case 2: {
-                    H2Args a = h2_args_fc1<NP>(s, w[2], D, G, plain);
-                    H2D_PHASE(H2_EPI_GELU, true, 2);
-                    break;
-                }
-                default: {
-                    const bool fc2 = (ph & 3) == 3;
-                    H2Args a = h2_args_res<NP>(s, fc2 ? w[3] : w[1], fc2, D, G, plain);
-                    H2D_PHASE(H2_EPI_RES, false, 1);
-                    break;
-                }
-            }
-#undef H2D_PHASE
-            if (!ok) return;
-        }
-    }
-}
+#define H2_WALK_KERNEL h2_stackd_kernel
+#define H2_WALK_FORM 2
+#include "h2_stack_walk.inc"
 
 // ---------------------------------------------------------------------------------------------- host side
 unsigned long long* h2_debug_buffer();       // h2_gemm.hip (test hooks shared by both engines)
@@ -2042,14 +1846,8 @@ static int h2_launch_stack(float* x, unsigned short* x16, int M, int D, int n_to
     if constexpr (NP == 2) {
         if (int rc = kernel_lds_once<h2_stack2_kernel<2>>(H2_LDS_BYTES, 512)) return rc;
     }
-    static std::atomic<int> n_cus[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return MPL_E_LAUNCH;
-    int cus = n_cus[dev].load(std::memory_order_acquire);
-    if (cus == 0) {
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) return MPL_E_LAUNCH;
-        n_cus[dev].store(cus, std::memory_order_release);
-    }
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64 || device_cu_count(&cus) != MPL_OK) return MPL_E_LAUNCH;
     H2StackArgs a;
     a.att2 = reinterpret_cast<char*>(att2);
     a.hid2 = reinterpret_cast<char*>(hid2);
@@ -2103,14 +1901,14 @@ static int h2_launch_stack(float* x, unsigned short* x16, int M, int D, int n_to
     {
         ProfScope prof(MPL_K_GEMM, s);
         rc = MPL_OK;
-        if (form.direct) rc = launch_h2d_stack(a, ((a.n_teams + 7) / 8) * 8 * a.G, s);
-        else if (a.rgs != 4) rc = launch_h2n_stack(a, ((a.n_teams + 7) / 8) * 8 * a.G, s);
-        else if constexpr (NP == 2) {
-            if (pairs) hipLaunchKernelGGL(h2_stack2_kernel<2>, dim3(((a.n_teams + 7) / 8) * 8 * a.G), dim3(512), H2_LDS_BYTES, s, a);
-            else hipLaunchKernelGGL(h2_stack_kernel<2>, dim3(((a.n_teams + 7) / 8) * 8 * a.G), dim3(512), H2_LDS_BYTES, s, a);
-        } else {
-            hipLaunchKernelGGL(h2_stack_kernel<1>, dim3(((a.n_teams + 7) / 8) * 8 * a.G), dim3(512), H2_LDS_BYTES, s, a);
+        const int grid = ((a.n_teams + 7) / 8) * 8 * a.G;        // whole XCD rounds
+        void (*whole)(const H2StackArgs) = h2_stack_kernel<NP>;
+        if constexpr (NP == 2) {
+            if (pairs) whole = h2_stack2_kernel<2>;
         }
+        if (form.direct) rc = launch_h2d_stack(a, grid, s);
+        else if (a.rgs != 4) rc = launch_h2n_stack(a, grid, s);
+        else hipLaunchKernelGGL(whole, dim3(grid), dim3(512), H2_LDS_BYTES, s, a);
         if (rc == MPL_OK) rc = hip_check_launch();
     }
     if (hipEventRecord(ev, s) != hipSuccess) return MPL_E_LAUNCH;

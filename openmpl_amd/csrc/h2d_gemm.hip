@@ -1,9 +1,5 @@
-// Direct-W form of the 16-row teams of the fp16x2 block stack (h2_phase.hpp h2_stackd_kernel), a translation unit of its own
+// Direct-W form of the 16-row teams of the fp16x2 block stack (h2_stackd_kernel: form 2 of h2_stack_walk.inc), a translation unit of its own
 // so that it compiles beside h2_gemm.hip / h2n_gemm.hip.
-#include <stdlib.h>
-
-#include <mutex>
-
 #include "h2_phase.hpp"
 
 namespace mpl {

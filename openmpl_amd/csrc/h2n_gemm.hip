@@ -1,13 +1,9 @@
-// Row-narrow form of the fp16x2 block stack (h2_phase.hpp h2_stackn_kernel), a translation unit of its own so that it compiles
+// Row-narrow form of the fp16x2 block stack (h2_stackn_kernel: form 1 of h2_stack_walk.inc), a translation unit of its own so that it compiles
 // beside h2_gemm.hip: the persistent stack kernel for launches that would leave most of the chip idle -- the reference's
 // shipped call shape (configs/h36m/mpl_amass/h36m.yaml:37-39,107: TEST.BATCH_SIZE 256, two views; loop
 // lib/core/function_mpl.py:334-351) is 512 token rows = 8 row tiles x 4 column groups = 32 of 256 compute units for
 // h2_stack_kernel, which walks them in the 0.83 ms it needs for ANY number of tiles.  Here a 64-row tile is shared by 4 (2)
 // teams of 16 (32) rows; same arithmetic per output element, bitwise the same poses (tests/test_h2_gpu.py).
-#include <stdlib.h>
-
-#include <mutex>
-
 #include "h2_phase.hpp"
 
 namespace mpl {
