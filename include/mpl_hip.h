@@ -116,7 +116,10 @@ typedef struct mpl_block_weights {
      * norm2 folded); proj_h2 / fc2_h2 from mpl_pack_h2_scaled against the static output scales of the layer that produces their
      * input: in_scale = mpl_pack_h2_out_scale(qkv_h2, 3D, D) + 2D (the v columns) for proj, mpl_pack_h2_out_scale(fc1_h2, 2D, D)
      * for fc2.  The stack verifies that pairing on the device (fingerprints inside the operands) and poisons the call's output
-     * (NaN poses, MPL_E_DEVICE) on a mismatch. */
+     * (NaN poses, MPL_E_DEVICE) on a mismatch.  The team kernels take widths 544 and 1088 (no LayerNorm folds into an operand beyond
+     * K = 1088) with a head dim that divides 136 and is a multiple of 4, while the score matrices of a slice fit the LDS beside
+     * the q | k | v tile (head dim 8: up to 14 tokens per sequence, head dim 4: up to 6); for every other stack the four fields
+     * are ignored and the nn.Linear tensors above run (mpl_block_stack_form: MPL_FORM_UNPACKED). */
     const uint16_t *qkv_h2, *proj_h2, *fc1_h2, *fc2_h2;
 } mpl_block_weights;
 
@@ -242,6 +245,12 @@ int mpl_pack_bf16(const float *W, const float *bias, const float *ln_w, const fl
  * MPL_BF16_NONE = the shape has no bf16 engine (more than 32 tokens per sequence: the joints x views token grid).  No device needed. */
 enum { MPL_BF16_NONE = 0, MPL_BF16_TUNED = 1, MPL_BF16_ANY = 2 };
 int mpl_bf16_operand_layout(int dim, int heads, int n_tok);
+/* 1 when the packed-operand team kernels (fp16x2: csrc/h2_gemm.hip, bf16: csrc/b1_gemm.hip) take a stack of this shape, 0 when not,
+ * MPL_E_INVALID for a non-positive argument -- the ONE rule behind mpl_block_stack(_ex), mpl_block_stack_form(_ex) and
+ * mpl_bf16_operand_layout: width 544 or 1088, a head dim that divides 136 and is a multiple of 4, and the score matrices of a slice
+ * in LDS beside the q | k | v tile (n_tok <= 32; head dim 8: <= 14, head dim 4: <= 6).  Whoever packs fp16x2 operands asks it first
+ * (mpl_pack_h2 folds no LayerNorm into an operand beyond K = 1088).  No device needed. */
+int mpl_team_stack_shape(int dim, int heads, int n_tok);
 
 /* Packed bf16 operand of an nn.Linear layer (W[N][K], bias[N]) for the shape-general bf16 engine (csrc/b1_any.hip), any
  * 1 <= N <= 16384, 1 <= K <= 8192: bf16(gamma o W) (round to nearest even of the fp32 product; gamma = 1 without a LayerNorm) as

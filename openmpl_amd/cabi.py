@@ -122,7 +122,7 @@ class Inputs(C.Structure):
 
 EXPORTS = ("mpl_hip_abi_version", "mpl_hip_error_string", "mpl_config_supported", "mpl_fpt_width", "mpl_forward_workspace_bytes",
            "mpl_forward", "mpl_spt_tokens", "mpl_block_stack_workspace_bytes", "mpl_block_stack", "mpl_block_stack_ex",
-           "mpl_ln_linear", "mpl_spt_pack_bytes", "mpl_spt_pack", "mpl_d32_pack", "mpl_pack_bf16_bytes", "mpl_pack_bf16", "mpl_bf16_operand_layout", "mpl_pack_bf16_any_bytes", "mpl_pack_bf16_any", "mpl_ln_linear_bf16_any_workspace_bytes", "mpl_ln_linear_bf16_any", "mpl_pack_h2_bytes", "mpl_pack_h2", "mpl_pack_h2_scaled", "mpl_pack_h2_out_scale", "mpl_ln_linear_h2_workspace_bytes", "mpl_ln_linear_h2", "mpl_x3_debug_buffer", "mpl_x3_stack_mode", "mpl_block_stack_form", "mpl_block_stack_form_ex", "mpl_block_stack_last_form", "mpl_spt_form", "mpl_device_error", "mpl_device_error_clear", "mpl_x3_spin_limit", "mpl_token_attention", "mpl_fuse_head", "mpl_view_fuse", "mpl_view_norm",
+           "mpl_ln_linear", "mpl_spt_pack_bytes", "mpl_spt_pack", "mpl_d32_pack", "mpl_pack_bf16_bytes", "mpl_pack_bf16", "mpl_bf16_operand_layout", "mpl_team_stack_shape", "mpl_pack_bf16_any_bytes", "mpl_pack_bf16_any", "mpl_ln_linear_bf16_any_workspace_bytes", "mpl_ln_linear_bf16_any", "mpl_pack_h2_bytes", "mpl_pack_h2", "mpl_pack_h2_scaled", "mpl_pack_h2_out_scale", "mpl_ln_linear_h2_workspace_bytes", "mpl_ln_linear_h2", "mpl_x3_debug_buffer", "mpl_x3_stack_mode", "mpl_block_stack_form", "mpl_block_stack_form_ex", "mpl_block_stack_last_form", "mpl_spt_form", "mpl_device_error", "mpl_device_error_clear", "mpl_x3_spin_limit", "mpl_token_attention", "mpl_fuse_head", "mpl_view_fuse", "mpl_view_norm",
            "mpl_layernorm", "mpl_linear", "mpl_pose_metrics_size", "mpl_pose_metrics", "mpl_pose_metrics_ex", "mpl_eval_state_bytes", "mpl_eval_reset", "mpl_eval_accumulate", "mpl_eval_report_size", "mpl_eval_report", "mpl_prepare_inputs", "mpl_decode_heatmaps", "mpl_decode_heatmaps_ex", "mpl_render_heatmaps", "mpl_rpsm_workspace_bytes", "mpl_rpsm", "mpl_synthesize_views", "mpl_triangulate_rays", "mpl_epipolar_errors", "mpl_triangulate_robust", "mpl_procrustes_align", "mpl_profile_start",
            "mpl_profile_stop")
 KINDS = ("spt", "row_stats", "gemm", "attention", "fuse_head", "pack")
@@ -203,6 +203,8 @@ def load():
         lib.mpl_pack_bf16.argtypes = [_fp, _fp, _fp, _fp, C.c_int, C.c_int, _fp, _fp]
         lib.mpl_bf16_operand_layout.restype = C.c_int
         lib.mpl_bf16_operand_layout.argtypes = [C.c_int, C.c_int, C.c_int]
+        lib.mpl_team_stack_shape.restype = C.c_int
+        lib.mpl_team_stack_shape.argtypes = [C.c_int, C.c_int, C.c_int]
         lib.mpl_pack_bf16_any_bytes.restype = C.c_size_t
         lib.mpl_pack_bf16_any_bytes.argtypes = [C.c_int, C.c_int]
         lib.mpl_pack_bf16_any.restype = C.c_int

@@ -157,13 +157,20 @@ StackWs carve_stack_ws(void* base, size_t M, size_t D) {
 
 std::atomic<int> g_spin_log2{23};    // polls before a wait inside a persistent kernel counts as lost (mpl_x3_spin_limit)
 
+// THE rule for "the packed-operand team kernels (h2_gemm.hip / b1_gemm.hip) take a stack of this shape": a head that tiles the
+// 136-column slice with its score matrices in LDS (h2_attention_fusable), a packed layout for every Linear, and D <= 1088: the
+// LayerNorm GEMMs (K = D) combine at most 8 slice partials per row, so launch_pack_h2 / launch_pack_b1 fold no LayerNorm into a
+// wider operand -- wider multiples of 544 run on the nn.Linear tensors (fp32) or on the shape-general bf16 engine
+bool team_stack_shape_ok(int n_tok, int D, int H) {
+    return D <= 1088 && h2_attention_fusable(n_tok, D, H) && h2_shape_ok(D, 2 * D);
+}
+
 // THE rule for "which bf16 operand layout do the *_w16 fields of a stack of this shape carry" (mpl_bf16_operand_layout): the tuned
 // one of mpl_pack_bf16 where the team kernels take the shape (b1_gemm.hip), else the shape-general one of mpl_pack_bf16_any
 // (b1_any.hip: any width up to 4096, any head count that divides it, up to 32 tokens per sequence), else none
 int bf16_layout(int D, int H, int n_tok) {
     if (D <= 0 || H <= 0 || n_tok <= 0) return MPL_E_INVALID;
-    // (D <= 1088: launch_pack_b1 / launch_b1_gemm combine at most 8 LayerNorm slice partials per row; wider multiples of 544 fall through)
-    if (D <= 1088 && h2_attention_fusable(n_tok, D, H) && h2_shape_ok(D, 2 * D)) return MPL_BF16_TUNED;
+    if (team_stack_shape_ok(n_tok, D, H)) return MPL_BF16_TUNED;
     if (n_tok <= 32 && D % H == 0 && D <= 4096 && b1a_operand_bytes(3 * D, D) && b1a_operand_bytes(D, 2 * D)) return MPL_BF16_ANY;
     return MPL_BF16_NONE;
 }
@@ -177,10 +184,10 @@ int engine_parts(int parts, int n_tok, int D, int H) {
         const int lay = bf16_layout(D, H, n_tok);
         return lay == MPL_BF16_TUNED ? 1 : (lay == MPL_BF16_ANY ? NP_BF16_ANY : 0);
     }
-    return (parts == 2 && h2_attention_fusable(n_tok, D, H) && h2_shape_ok(D, 2 * D)) ? 2 : 0;
+    return (parts == 2 && team_stack_shape_ok(n_tok, D, H)) ? 2 : 0;
 }
-int stack_packed_parts(const mpl_block_weights* blocks, const uint8_t* schedule, int n_apps, int n_tok, int D, int H) {
-    if (n_apps <= 0) return 0;
+// what every scheduled block carries: 1 = the four *_w16 operands, 2 = the four *_h2 operands, 0 = neither, or not all the same
+int stack_carried_parts(const mpl_block_weights* blocks, const uint8_t* schedule, int n_apps) {
     int np = 0;
     for (int a = 0; a < n_apps; ++a) {
         const mpl_block_weights& b = blocks[schedule[a]];
@@ -188,7 +195,7 @@ int stack_packed_parts(const mpl_block_weights* blocks, const uint8_t* schedule,
         if (bp == 0 || (np && bp != np)) return 0;
         np = bp;
     }
-    return engine_parts(np, n_tok, D, H);
+    return np;
 }
 
 // Workspace of the shape-general bf16 engine (b1_any.hip): x stays fp32 in place; qkv fp32 (the attention reads it), the attention
@@ -330,16 +337,22 @@ int block_stack_impl(float* x, int n_seq, int n_tok, int D, int H, const mpl_blo
     // row counts are 32-bit in the kernels (byte offsets are 64-bit): refuse what would overflow instead of wrapping
     if ((long long)n_seq * n_tok > (1ll << 30)) return MPL_E_UNSUPPORTED;
     if (n_apps == 0) return MPL_OK;
+    // one limit for every engine, the one mpl_block_stack_form_ex answers by (the fp32-MFMA route had none of its own)
+    if (n_apps > MPL_MAX_APPS) return MPL_E_UNSUPPORTED;
     // the narrowest GEMM of a block (K = D) decides whether the any-K kernel runs it, and it must take the rows
     if (!ln_gemm_rows_ok((long long)n_seq * n_tok, D, D)) return MPL_E_UNSUPPORTED;
     if (!blocks || !schedule) return MPL_E_INVALID;
-    const int np0 = stack_packed_parts(blocks, schedule, n_apps, n_tok, D, H);
+    const int carried = stack_carried_parts(blocks, schedule, n_apps);
+    const int np0 = carried ? engine_parts(carried, n_tok, D, H) : 0;
+    // fp16x2 operands of a shape the team kernels do not take (a head dim 8 stack beyond 14 tokens: h2_attention_fusable) are an
+    // fp32 request all the same: the stack runs on the nn.Linear tensors, as mpl_block_stack_form reports (MPL_FORM_UNPACKED)
+    const bool ignore_h2 = carried == 2 && np0 == 0;
     // up to 80 token rows (a single frame, a few frames): the whole chip on every GEMM instead of one team of D / 136
     // workgroups (sm_stack.hip) -- for the fp32 engines; an explicit bf16 request keeps its engine
     // (not when the caller asked for batch-invariant bits -- MPL_F_NO_SMALL_STACK --, nor under the A/B switches of the team
     // kernels: one launch per GEMM, stop after n phases).  ONE predicate decides (small_engine_taken): this function launches
     // by it and mpl_block_stack_form reports by it.
-    if (n_apps <= MPL_MAX_APPS && (long long)n_seq * n_tok <= sm_stack_max_rows()) {
+    if ((long long)n_seq * n_tok <= sm_stack_max_rows()) {
         int n_blocks = 0;
         bool raw = true;        // the engine reads the nn.Linear tensors in place: a caller that hands over packed operands only
         for (int a = 0; a < n_apps; ++a) {      // (the C ABI allows it) gets the team kernels, not an error
@@ -403,12 +416,20 @@ int block_stack_impl(float* x, int n_seq, int n_tok, int D, int H, const mpl_blo
         }
         return MPL_OK;
     }
+    // every scheduled block is looked at before the first launch: a refusal leaves x untouched.  Packed operands (fp16x2 / bf16)
+    // take the routes above and cannot be used here, except fp16x2 operands without an engine (ignore_h2), which are not read --
+    // the nn.Linear tensors must then be there
     for (int a = 0; a < n_apps; ++a) {
         const mpl_block_weights& b = blocks[schedule[a]];
-            // packed operands (fp16x2 / bf16) take the routes above; here they cannot be used
-        if (b.qkv_w3 || b.proj_w3 || b.fc1_w3 || b.fc2_w3 || b.qkv_w16 || b.proj_w16 || b.fc1_w16 || b.fc2_w16 || b.qkv_h2 ||
-            b.proj_h2 || b.fc1_h2 || b.fc2_h2)
+        if (b.qkv_w3 || b.proj_w3 || b.fc1_w3 || b.fc2_w3 || b.qkv_w16 || b.proj_w16 || b.fc1_w16 || b.fc2_w16 ||
+            (!ignore_h2 && (b.qkv_h2 || b.proj_h2 || b.fc1_h2 || b.fc2_h2)))
             return MPL_E_UNSUPPORTED;
+        if (ignore_h2 && !(b.ln1_w && b.ln1_b && b.qkv_w && b.qkv_b && b.proj_w && b.proj_b && b.ln2_w && b.ln2_b && b.fc1_w && b.fc1_b &&
+                           b.fc2_w && b.fc2_b))
+            return MPL_E_UNSUPPORTED;
+    }
+    for (int a = 0; a < n_apps; ++a) {
+        const mpl_block_weights& b = blocks[schedule[a]];
         const bool fused_att = fusable;
         // x = x + proj(attn(qkv(norm1(x))))   (Block.forward :84-90)
         if (!have_stats && (rc = launch_row_stats(x, M, D, D, w.stats, s))) return rc;
@@ -614,6 +635,10 @@ int mpl_pack_bf16(const float* W, const float* bias, const float* ln_w, const fl
 }
 
 int mpl_bf16_operand_layout(int dim, int heads, int n_tok) { return bf16_layout(dim, heads, n_tok); }
+int mpl_team_stack_shape(int dim, int heads, int n_tok) {
+    if (dim <= 0 || heads <= 0 || n_tok <= 0) return MPL_E_INVALID;
+    return team_stack_shape_ok(n_tok, dim, heads) ? 1 : 0;
+}
 
 size_t mpl_pack_bf16_any_bytes(int N, int K) { return b1a_operand_bytes(N, K); }
 

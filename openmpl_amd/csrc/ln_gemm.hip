@@ -135,6 +135,25 @@ struct Frag {
     float4 b[NT];
 };
 
+// Dot products longer than ACC_CHAIN_MAX columns are accumulated in chunks of ACC_CHUNK k-tiles (512 columns): after every chunk the
+// running accumulator is added to a second one and cleared (kernel parameter CHUNKED).  One chain over all of K loses sqrt(K / 4)
+// roundings of the whole partial sum -- per token row at K = 7616 six times the error of a float32 reference that sums in blocks --;
+// in chunks a chain is 128 matrix instructions long at any K.  The second accumulator set costs 36 registers, which the 4-wave
+// (NG = 1) kernel has and the 12-wave (NG = 3) and column-split kernels (168 registers per lane) have not: K > ACC_CHAIN_MAX always
+// runs ln_gemm_ng_kernel<.., NG = 1, .., CHUNKED = true> (launch_ng_auto; the fused qkv + attention kernel is NG = 3 and stops at
+// ACC_CHAIN_MAX, qkv_attention_fusable).  The choice depends on K alone, so the k order of an output element stays independent of
+// the launch; up to ACC_CHAIN_MAX (the longest dot product of the tuned widths 544 and 1088: fc2 at 1088) every kernel is one chain.
+constexpr int ACC_CHUNK = 16;
+constexpr int ACC_CHAIN_MAX = 2176;
+template <int N_>
+__device__ __forceinline__ void acc_flush(f32x4 (&tot)[N_], f32x4 (&acc)[N_]) {
+#pragma unroll
+    for (int n = 0; n < N_; ++n) {
+        tot[n] += acc[n];
+        acc[n] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+}
+
 // fragments of 16-deep k step `step` (sub-tile step >> 1, half step & 1) of the stage at `st`
 template <bool LN, int NG>
 __device__ __forceinline__ void load_frag(Frag& f, const char* st, int step, int rg, int cg, int li, int kq, int swz) {
@@ -159,7 +178,7 @@ __device__ __forceinline__ void load_frag(Frag& f, const char* st, int step, int
 // q, k, v of 136 / hd heads for its 64 rows = 64 / n_tok whole sequences and finishes Attention.forward :55-64
 // in its epilogue (scores, softmax, P.V through LDS): the packed qkv tensor never goes to memory.
 // One k-tile per stage; every wave issues its share of the DMA pieces and owns its counted waits.
-template <int EPI, bool LN, int NG, int NST, bool ATT = false>
+template <int EPI, bool LN, int NG, int NST, bool ATT = false, bool CHUNKED = false>
 __global__ __launch_bounds__(256 * NG, 1) void ln_gemm_ng_kernel(const float* __restrict__ A, int lda,
                                                                  const float* __restrict__ stats,
                                                                  const float* __restrict__ ln_w,
@@ -171,6 +190,7 @@ __global__ __launch_bounds__(256 * NG, 1) void ln_gemm_ng_kernel(const float* __
                                                                  float* stats_out, int att_ntok, int att_hd,
                                                                  float* att_out) {
     static_assert(!ATT || (NG == 3 && EPI == MPL_EPI_BIAS), "fused attention needs the q|k|v geometry");
+    static_assert(!CHUNKED || NG == 1, "the second accumulator set fits the 4-wave kernel only");
     // KS k-tiles per stage, KG k groups (waves that split the k steps of a stage): both 1 in every shipped geometry.  The loops
     // below keep their general form: flattened by hand, they compile to other register assignments (other instructions).
     constexpr int KS = 1, KG = 1;
@@ -292,6 +312,11 @@ __global__ __launch_bounds__(256 * NG, 1) void ln_gemm_ng_kernel(const float* __
     f32x4 acc[NT];
 #pragma unroll
     for (int n = 0; n < NT; ++n) acc[n] = f32x4{0.f, 0.f, 0.f, 0.f};
+    f32x4 tot[CHUNKED ? NT : 1];                // CHUNKED: the sum of the finished chunks
+    if constexpr (CHUNKED) {
+#pragma unroll
+        for (int n = 0; n < NT; ++n) tot[n] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
 
     if (!LN) __syncthreads();                   // zero fill above is ordinary LDS traffic: order it first
 #pragma unroll
@@ -351,6 +376,14 @@ __global__ __launch_bounds__(256 * NG, 1) void ln_gemm_ng_kernel(const float* __
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
+        if constexpr (CHUNKED) {
+            static_assert(KS == 1, "a stage is one k-tile: the chunks end on stage boundaries");
+            if (((t + 1) & (ACC_CHUNK - 1)) == 0) acc_flush(tot, acc);
+        }
+    }
+    if constexpr (CHUNKED) {
+#pragma unroll
+        for (int n = 0; n < NT; ++n) acc[n] += tot[n];
     }
     if (ATT) {
         // ---- fused attention epilogue.  T[64][412]: q | k | v (+bias) of this workgroup's 136 channels.
@@ -377,7 +410,7 @@ __global__ __launch_bounds__(256 * NG, 1) void ln_gemm_ng_kernel(const float* __
                              stats_out, N / BN);
 }
 
-template <int EPI, bool LN, int NG, int NST, bool ATT = false>
+template <int EPI, bool LN, int NG, int NST, bool ATT = false, bool CHUNKED = false>
 static int launch_ng(const float* A, int lda, const float* stats, const float* ln_w, const float* ln_b, const float* W,
                      const float* bias, const float* R, int ldr, float* C, int ldc, int M, int N, int K, float eps,
                      float* stats_out, hipStream_t s, int att_ntok = 0, int att_hd = 0, float* att_out = nullptr) {
@@ -385,9 +418,10 @@ static int launch_ng(const float* A, int lda, const float* stats, const float* l
     static_assert(LDS <= 160 * 1024, "LDS ring too large");
     const int gm = (M + BM - 1) / BM, gn = (N + BN * NG - 1) / (BN * NG);
     static_assert(!ATT || (BM * (3 * BN + 4) + ATT_SCORE_FLOATS) * 4 <= LDS, "attention epilogue does not fit in the ring");
-    if (int rc = kernel_lds_once<ln_gemm_ng_kernel<EPI, LN, NG, NST, ATT>>(LDS)) return rc;
+    if (CHUNKED != (K > ACC_CHAIN_MAX)) return MPL_E_INVALID;       // one accumulation per K, whatever the launch
+    if (int rc = kernel_lds_once<ln_gemm_ng_kernel<EPI, LN, NG, NST, ATT, CHUNKED>>(LDS)) return rc;
     ProfScope prof(MPL_K_GEMM, s);
-    hipLaunchKernelGGL((ln_gemm_ng_kernel<EPI, LN, NG, NST, ATT>), dim3(gm * gn), dim3(256 * NG), LDS, s,
+    hipLaunchKernelGGL((ln_gemm_ng_kernel<EPI, LN, NG, NST, ATT, CHUNKED>), dim3(gm * gn), dim3(256 * NG), LDS, s,
                        A, lda, stats, ln_w, ln_b, W, bias, R, ldr, C, ldc, M, N, K, gm, gn, eps, stats_out, att_ntok,
                        att_hd, att_out);
     return hip_check_launch();
@@ -631,8 +665,18 @@ static int launch_ng_auto(const float* A, int lda, const float* stats, const flo
     // NG = 3 when it still yields >= 256 workgroups (one per CU).  Measured on MI355X (M = 4096, D = 544): QKV 80 us
     // with either geometry; the 4-wave workgroup wins for N = D and N = 2 D, k-group splitting never paid.
     const int gm = (M + BM - 1) / BM;
-    if (N % (BN * 3) == 0 && gm * (N / (BN * 3)) >= 256) return launch_ng<EPI, LN, 3, 2>(MPL_ARGS2);
     const int wgs = gm * ((N + BN - 1) / BN);
+    auto cost = [&](int k) {
+        const int rounds = (wgs + 256 * k - 1) / (256 * k);
+        const int per_cu = (wgs + 255) / 256;
+        return rounds * (per_cu < k ? per_cu : k);
+    };
+    // K > ACC_CHAIN_MAX: chunked accumulation, which only the 4-wave kernel has the registers for (ring depth as below)
+    if (K > ACC_CHAIN_MAX) {
+        if (cost(3) <= cost(2)) return launch_ng<EPI, LN, 1, 2, false, true>(MPL_ARGS2);
+        return launch_ng<EPI, LN, 1, 3, false, true>(MPL_ARGS2);
+    }
+    if (N % (BN * 3) == 0 && gm * (N / (BN * 3)) >= 256) return launch_ng<EPI, LN, 3, 2>(MPL_ARGS2);
     // One workgroup per CU (or two of the register-light non-residual variants): the 8-wave column-split kernel
     // with its loader wave.  Measured on MI355X at M = 4096, D = 544 against the best 4-wave configuration:
     // proj 29.1 -> 27.1 us, fc2 52.2 -> 48.7 us, fc1 (512 workgroups, two per CU) 56.0 -> 52.0 us; with more
@@ -643,22 +687,18 @@ static int launch_ng_auto(const float* A, int lda, const float* stats, const flo
     // independent workgroups per CU hide each other's barrier bubbles better than a deeper ring does (measured:
     // proj 32 vs 35 us, fc2 57 vs 61 us at D = 544), unless 3 per CU quantises badly (1024 workgroups = 1.33
     // rounds of 768 slots): pick the occupancy with the fewer CU-time units, ties go to 3 per CU.
-    auto cost = [&](int k) {
-        const int rounds = (wgs + 256 * k - 1) / (256 * k);
-        const int per_cu = (wgs + 255) / 256;
-        return rounds * (per_cu < k ? per_cu : k);
-    };
     if (cost(3) <= cost(2)) return launch_ng<EPI, LN, 1, 2>(MPL_ARGS2);
     return launch_ng<EPI, LN, 1, 3>(MPL_ARGS2);
 #undef MPL_ARGS2
 }
 
 // LN1 + qkv projection + softmax attention in one launch: att[M, D] from x[M, D].  Requirements (else the caller
-// uses the separate kernels): 136 % hd == 0, 64 % n_tok == 0, D % 136 == 0 and D % 32 == 0 (whole k-tiles).
+// uses the separate kernels): 136 % hd == 0, 64 % n_tok == 0, D % 136 == 0 and D % 32 == 0 (whole k-tiles),
+// D <= ACC_CHAIN_MAX (the kernel is NG = 3: one accumulator chain).
 bool qkv_attention_fusable(int n_tok, int dim, int heads) {
     if (heads <= 0 || dim % heads) return false;
     const int hd = dim / heads;
-    return dim % BN == 0 && dim % BK == 0 && BN % hd == 0 && (hd & 3) == 0 && n_tok >= 1 && BM % n_tok == 0 && n_tok * n_tok * (BN / hd) * (BM / n_tok) <= ATT_SCORE_FLOATS;
+    return dim <= ACC_CHAIN_MAX && dim % BN == 0 && dim % BK == 0 && BN % hd == 0 && (hd & 3) == 0 && n_tok >= 1 && BM % n_tok == 0 && n_tok * n_tok * (BN / hd) * (BM / n_tok) <= ATT_SCORE_FLOATS;
 }
 
 int launch_ln_qkv_attention(const float* x, int M, int D, const float* stats, const float* ln_w, const float* ln_b,

@@ -385,9 +385,10 @@ class MultiView_MPL(nn.Module):
         return self
 
     def _x3_supported(self) -> bool:
-        """The packed-operand engines (fp16x2 / bf16) need every FPT Linear shape to have a packed layout (out features a
-        multiple of 136, in features of 544: widths 544 and 1088, i.e. every view-token model at DIM 32;
-        mpl_pack_bf16_bytes / mpl_pack_h2_bytes decide) and fuse the attention for up to 32 tokens per sequence."""
+        """The packed-operand team engines (fp16x2 / bf16 tuned layout) run this model's FPT stack: the library's rule
+        (mpl_team_stack_shape: width 544 or 1088 -- no LayerNorm folds into a wider operand --, a head dim that tiles the 136-column
+        slice, and the score matrices of num_views tokens in LDS: head dim 8 up to 14 views), and every FPT Linear shape has a
+        packed layout (mpl_pack_bf16_bytes / mpl_pack_h2_bytes).  Elsewhere "fp32" runs on the nn.Linear tensors."""
         c = self.__dict__.get("_x3_ok")
         if c is not None and c[0] == _STRUCT_GEN[0] and _HOOKS_OK:
             return c[1]
@@ -402,6 +403,7 @@ class MultiView_MPL(nn.Module):
             ok = all(lib.mpl_pack_bf16_bytes(int(t.shape[0]), int(t.shape[1])) > 0 and
                      lib.mpl_pack_h2_bytes(int(t.shape[0]), int(t.shape[1])) > 0
                      for t in (b.attn.qkv.weight, b.attn.proj.weight, b.mlp.fc1.weight, b.mlp.fc2.weight))
+            ok = ok and lib.mpl_team_stack_shape(D, self.num_heads, self.num_views) == 1
         self.__dict__["_x3_ok"] = (_STRUCT_GEN[0], ok)
         return ok
 

@@ -411,6 +411,60 @@ def test_the_reported_form_is_the_form_that_was_launched(name, B, prec):
     assert lib.mpl_block_stack_form_ex(1, 2, 544, 8, 13, 14, 1, 2, 0) < 0                     # more blocks than applications
 
 
+@pytest.mark.parametrize("J,d,H,V,B,why", [(17, 96, 12, 4, 30, "width 1632, head dim 136: no LayerNorm folds into an operand beyond K = 1088"),
+                                           (8, 68, 68, 15, 8, "width 544, head dim 8, 15 views: the score matrices of a slice do not fit the LDS"),
+                                           (8, 68, 68, 14, 8, "the same at 14 views: they fit, the team kernels run")])
+def test_predicate_and_launcher_agree_where_the_team_kernels_do_not_take_a_shape(J, d, H, V, B, why):
+    """ONE rule says which stacks the packed-operand team kernels take (csrc/api.hip team_stack_shape_ok, exported as
+    mpl_team_stack_shape): the form query, the launcher, the bf16 layout and MultiView_MPL._x3_supported all answer by it.  Width
+    at most 1088 (mpl_pack_h2 folds no LayerNorm into a wider operand: a model that packed first would raise at its first
+    forward) and the score matrices of a slice in LDS (head dim 8: up to 14 tokens).  Outside it an "fp32" model packs nothing and
+    runs on the nn.Linear tensors, and a C-ABI caller's fp16x2 operands are ignored, as the form query says (UNPACKED).  More
+    than 96 token rows here, so no call is the small engine's."""
+    lib = cabi.load()
+    flags = dict(num_joints=J, embed_dim_ratio=d, num_heads=H, depth=1, num_views=V, pose_3d_emb_learnable=True)
+    from openmpl_amd.multiview_mpl import MultiView_MPL
+    m = detrng.fill_module_(MultiView_MPL(**flags), seed=7)
+    assert m._unsupported is None, m._unsupported
+    sd = {k: v.detach().clone() for k, v in m.state_dict().items()}
+    m = m.to(DEV).eval()
+    D, teams = J * d, (d, V) == (68, 14)
+    assert B * V > 96 and m._x3_supported() == teams, why
+    assert lib.mpl_team_stack_shape(D, H, V) == int(teams) and (lib.mpl_bf16_operand_layout(D, H, V) == cabi.BF16_TUNED) == teams
+    asked = lib.mpl_block_stack_form(B, V, D, H, 2, 2, 0)            # "the blocks carry fp16x2 operands"
+    assert (asked != cabi.FORM_UNPACKED) == teams and asked >= 0, (asked, why)
+    p, r, c = detrng.make_inputs(B, V, J, seed=5)
+    P, R, Cn = ([torch.from_numpy(x) for x in lst] for lst in (p, r, c))
+    with torch.no_grad():
+        out = m([x.to(DEV) for x in P], rays=[x.to(DEV) for x in R], centers=[x.to(DEV) for x in Cn])
+    torch.cuda.synchronize()
+    assert lib.mpl_block_stack_last_form() == asked
+    assert bool(m._hip_cache[0]["fpt_blocks"][0].qkv_h2) == teams
+    _assert_close(out, mpl_oracle.forward(sd, flags, P, R, Cn, dtype=torch.float64), "J%d d%d H%d V%d" % (J, d, H, V))
+    if not teams:
+        # the C ABI: fp16x2 operands of a shape without an engine (packed at a width that has one: the LayerNorm-free proj operand
+        # stands in for all four -- they are not read) run the nn.Linear tensors, bitwise the call without them
+        blk = cabi.BlockWeights.from_buffer_copy(m._hip_cache[0]["fpt_blocks"][0])
+        x = torch.randn(B * V, D, generator=torch.Generator().manual_seed(1)).to(DEV)
+        wsb = lib.mpl_block_stack_workspace_bytes(B, V, D)
+        ws = torch.empty(wsb, dtype=torch.uint8, device=DEV)
+        sched = (C.c_uint8 * 2)(0, 0)
+        outs = []
+        for with_h2 in (False, True):
+            y = x.clone()
+            if with_h2:
+                pk = torch.zeros(lib.mpl_pack_h2_bytes(D, D), dtype=torch.uint8, device=DEV)
+                cabi.check(lib.mpl_pack_h2(m.blocks[0].attn.proj.weight.data_ptr(), m.blocks[0].attn.proj.bias.data_ptr(), None, None,
+                                           D, D, pk.data_ptr(), _stream()), "mpl_pack_h2")
+                blk.qkv_h2 = blk.proj_h2 = blk.fc1_h2 = blk.fc2_h2 = pk.data_ptr()
+            cabi.check(lib.mpl_block_stack_ex(y.data_ptr(), B, V, D, H, C.byref(blk), sched, 2, ws.data_ptr(), wsb, 0, _stream()),
+                       "mpl_block_stack_ex")
+            torch.cuda.synchronize()
+            assert lib.mpl_block_stack_last_form() == cabi.FORM_UNPACKED
+            outs.append(y)
+        assert torch.isfinite(outs[0]).all() and torch.equal(outs[0], outs[1])
+
+
 @pytest.mark.parametrize("name,B", [("chosen_v4_b8_l12", 512), ("chosen_v4_b8_l2", 48), ("chosen_v4_b8_l2", 1), ("full_v4_b8_l2", 200),
                                     ("chosen_v5_b19_l2", 100), ("chosen_v31_b2_l12", 9), ("chosen_v8_b4_l2", 37), ("chosen_v2_b1_l12", 97)])
 def test_two_tile_stage_is_bitwise_the_one_tile_stage(name, B):
