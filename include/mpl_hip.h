@@ -34,6 +34,10 @@
  *   mpl_decode_heatmaps_ex the same with a sub-pixel peak: the intent of lib/core/inference.py:84-134 (find_tensor_peak_batch)
  *   mpl_render_heatmaps    lib/dataset/joints_dataset_mpl.py:828-870 (generate_heatmap)
  *   mpl_rpsm               lib/multiviews/pictorial.py:18-247 (rpsm, recursive_infer, infer, compute_unary_term, compute_grid)
+ *   mpl_undistort_points   lib/multiviews/cameras.py:22-46 (project_point_radial) and its inverse, which the reference leaves to
+ *                          pymvg on the host (lib/multiviews/triangulate.py:26-38)
+ *   mpl_prepare_inputs_ex  mpl_prepare_inputs for a calibration with k, p (lib/dataset/joints_dataset_mpl.py:269, :337)
+ *   mpl_synthesize_views_ex  mpl_synthesize_views with the projection of lib/multiviews/cameras.py:22-46
  */
 #ifndef MPL_HIP_H_
 #define MPL_HIP_H_
@@ -573,6 +577,53 @@ int mpl_synthesize_views(const float *poses3d, const double *cams_dev, const mpl
                          const float *rotation_deg, const float *translation, const float *noise, const float *missing_u,
                          int batch, int views, int joints, float *const *poses, float *const *rays, float *const *centers,
                          float *target, float *pixels, float *pixels_clean, float *depth, void *stream);
+
+/* ---- lens distortion, csrc/views.hpp and csrc/distortion.hip: one model for every call that projects or builds a ray.
+ * The distortion record is dist_dev, device (V,5) float64 k1 k2 k3 p1 p2 per view, the layout mpl_rpsm takes.  With y = x_cam.xy / z
+ * and r2 = |y|^2 the lens maps y to  y_d = y g + (p2, p1) r2,  g = 1 + (k1 r2 + k2 r2^2 + k3 r2^3) + (2 p1 y.y + 2 p2 y.x),  and
+ * the pixel is f y_d + c: the reference's project_point_radial (lib/multiviews/cameras.py:22-46), the form of the H36M toolbox.  It
+ * is NOT OpenCV's model, whose tangential terms are 2 p1 x y + p2 (r2 + 2 x^2) and p1 (r2 + 2 y^2) + 2 p2 x y.  The reference is not
+ * consistent here: lib/multiviews/triangulate.py:26-38 hands the same five numbers, reordered to (k1 k2 p1 p2 k3), to pymvg, which
+ * undistorts with OpenCV's model.  This library inverts the model it projects with.
+ * The inverse is Newton's iteration in fp64 from y = y_d with the analytic 2x2 Jacobian J: at most 20 iterations (the
+ * calibrations of Human3.6M and CMU Panoptic take 6); done when max |step| <= 1e-14 * max(1, |y|_inf); an iterate with det J <= 0
+ * (the point lies beyond the fold of the polynomial, where no pinhole point maps to it), a non-finite value or an exhausted cap
+ * makes the point NOT INVERTIBLE.  With all-zero coefficients the first residual is exactly 0 and y = y_d bit for bit.
+ *
+ * mpl_undistort_points: one launch, one work item per (b, v, j), fp64 on the fp32 pixel (x, y) of pixels (B,V,J,2).
+ * MPL_DISTORT_REMOVE: y_d = ((x - cx) / fx, (y - cy) / fy), y_u its inverse, out = (x + fx (y_u.x - y_d.x), y + fy (y_u.y - y_d.y)),
+ * rounded once: zero coefficients return the input.  A point that is not invertible gives NaN in both coordinates and valid = 0.
+ * MPL_DISTORT_APPLY: the forward polynomial on a pinhole pixel, in the same form: y = ((x - cx) / fx, (y - cy) / fy),
+ * out = (x + fx (y_d.x - y.x), y + fy (y_d.y - y.y)); always valid.
+ * out_pixels (B,V,J,2) fp32; out_valid (B,V,J) bytes of 0 / 1, or NULL.  cams_dev as for mpl_prepare_inputs.
+ * MPL_E_INVALID: pixels, cams_dev, dist_dev or out_pixels NULL, a non-positive size, views > MPL_MAX_VIEWS, an unknown direction;
+ * MPL_E_UNSUPPORTED: batch * views * joints > 2^30 -- before any launch.  Stream-ordered, never synchronises; neither looks at nor
+ * sets the device error word. */
+#define MPL_DISTORT_REMOVE 0
+#define MPL_DISTORT_APPLY 1
+int mpl_undistort_points(const float *pixels, const double *cams_dev, const double *dist_dev, int batch, int views, int joints,
+                         int direction, float *out_pixels, unsigned char *out_valid, void *stream);
+
+/* mpl_prepare_inputs with a lens.  poses are what they are without it: the observed pixel, normalised as the switches say, plus
+ * the confidence.  The ray goes through the undistorted pixel (x + fx D.x, y + fy D.y), D = y_u - y_d formed from the raw
+ * intrinsics before any normalisation, on which the ray arithmetic of mpl_prepare_inputs then runs.  A joint that is not invertible
+ * keeps its pinhole ray and gets confidence 0 in poses[..., 2], like a missing joint: mpl_triangulate_rays, mpl_triangulate_robust
+ * and mpl_epipolar_errors then leave that view out.  dist_dev == NULL launches the kernel of mpl_prepare_inputs: same bits.  Zero
+ * coefficients give those bits too.  Arguments and refusals otherwise as for mpl_prepare_inputs. */
+int mpl_prepare_inputs_ex(const float *joints_px, const float *conf, const double *cams_dev, const double *dist_dev, int batch,
+                          int views, int joints, float img_w, float img_h, int normalize_inputs, int normalize_cameras,
+                          float *const *poses, float *const *rays, float *const *centers, void *stream);
+
+/* mpl_synthesize_views with a lens.  Step 2 becomes px = (fx y_d.x + cx, fy y_d.y + cy) with y = x_cam.xy / z, the form of mpl_rpsm
+ * (under zero coefficients this rounds differently from fx x / z + cx: within fp64 rounding of the pinhole launch, not bitwise);
+ * pixels_clean, the noise, the visibility step and the missing-joint step act on distorted pixels, as a detector sees them; step 6
+ * is the arithmetic of mpl_prepare_inputs_ex on the fp64 pixel.  Depth, target and the z <= 1e-9 rule do not change.
+ * dist_dev == NULL launches the kernel of mpl_synthesize_views: same bits.  Arguments and refusals otherwise as for
+ * mpl_synthesize_views. */
+int mpl_synthesize_views_ex(const float *poses3d, const double *cams_dev, const double *dist_dev, const mpl_synth_options *opt,
+                            const float *conf, const float *rotation_deg, const float *translation, const float *noise,
+                            const float *missing_u, int batch, int views, int joints, float *const *poses, float *const *rays,
+                            float *const *centers, float *target, float *pixels, float *pixels_clean, float *depth, void *stream);
 
 /* ---- multi-view geometry on the tensors of mpl_inputs, csrc/geometry.hip: rays[v] (B,J,3) is a world point on the line of
  * sight of view v (joints_dataset_mpl.py:872-904), centers[v] (B,1,3) the camera centre; line v goes through c_v along

@@ -15,12 +15,15 @@ def __getattr__(name):
     if name == "PoseEvaluator":
         from .evaluate import PoseEvaluator
         return PoseEvaluator
-    if name in ("triangulate_rays", "triangulate_rays_robust", "epipolar_errors", "consistency_weights"):
+    if name in ("triangulate_rays", "triangulate_rays_robust", "triangulate_pixels", "epipolar_errors", "consistency_weights"):
         from . import geometry
         return getattr(geometry, name)
     if name == "procrustes_align":
         from .procrustes import procrustes_align
         return procrustes_align
+    if name in ("pack_distortion", "undistort_points", "distort_points"):
+        from . import inputs
+        return getattr(inputs, name)
     if name in ("synthesize_views", "project_points"):
         from . import synth
         return getattr(synth, name)

@@ -101,6 +101,9 @@ RENDER_MODES = {"reference": 0, "subpixel": 1}
 # mpl_rpsm(): the launches a call issues (MPL_RPSM_* of mpl_hip.h); anything but RPSM_ALL is a measurement
 RPSM_UNARY, RPSM_LEVELS, RPSM_FINAL, RPSM_ALL = 1, 2, 4, 7
 
+# mpl_undistort_points(): the directions (MPL_DISTORT_* of mpl_hip.h)
+DISTORT_REMOVE, DISTORT_APPLY = 0, 1
+
 # mpl_synthesize_views(): the confidence penalties (MPL_SYNTH_PENALIZE_* of mpl_hip.h) and the options struct
 SYNTH_PENALIZE = {"none": 0, "exp_error": 1, "linear": 2, "exp_sqrt": 3}
 
@@ -124,7 +127,10 @@ EXPORTS = ("mpl_hip_abi_version", "mpl_hip_error_string", "mpl_config_supported"
            "mpl_forward", "mpl_spt_tokens", "mpl_block_stack_workspace_bytes", "mpl_block_stack", "mpl_block_stack_ex",
            "mpl_ln_linear", "mpl_spt_pack_bytes", "mpl_spt_pack", "mpl_d32_pack", "mpl_pack_bf16_bytes", "mpl_pack_bf16", "mpl_bf16_operand_layout", "mpl_team_stack_shape", "mpl_pack_bf16_any_bytes", "mpl_pack_bf16_any", "mpl_ln_linear_bf16_any_workspace_bytes", "mpl_ln_linear_bf16_any", "mpl_pack_h2_bytes", "mpl_pack_h2", "mpl_pack_h2_scaled", "mpl_pack_h2_out_scale", "mpl_ln_linear_h2_workspace_bytes", "mpl_ln_linear_h2", "mpl_x3_debug_buffer", "mpl_x3_stack_mode", "mpl_block_stack_form", "mpl_block_stack_form_ex", "mpl_block_stack_last_form", "mpl_spt_form", "mpl_device_error", "mpl_device_error_clear", "mpl_x3_spin_limit", "mpl_token_attention", "mpl_fuse_head", "mpl_view_fuse", "mpl_view_norm",
            "mpl_layernorm", "mpl_linear", "mpl_pose_metrics_size", "mpl_pose_metrics", "mpl_pose_metrics_ex", "mpl_eval_state_bytes", "mpl_eval_reset", "mpl_eval_accumulate", "mpl_eval_report_size", "mpl_eval_report", "mpl_prepare_inputs", "mpl_decode_heatmaps", "mpl_decode_heatmaps_ex", "mpl_render_heatmaps", "mpl_rpsm_workspace_bytes", "mpl_rpsm", "mpl_synthesize_views", "mpl_triangulate_rays", "mpl_epipolar_errors", "mpl_triangulate_robust", "mpl_procrustes_align", "mpl_profile_start",
-           "mpl_profile_stop")
+           "mpl_profile_stop",
+           # lens distortion: lib/multiviews/cameras.py:22-46 (project_point_radial) and its inverse, which the reference leaves to pymvg
+           # (lib/multiviews/triangulate.py:26-38); the _ex calls are their namesakes for a calibration with k, p
+           "mpl_undistort_points", "mpl_prepare_inputs_ex", "mpl_synthesize_views_ex")
 KINDS = ("spt", "row_stats", "gemm", "attention", "fuse_head", "pack")
 
 _lib = None
@@ -294,6 +300,12 @@ def load():
         lib.mpl_synthesize_views.restype = C.c_int
         lib.mpl_synthesize_views.argtypes = [_fp, _fp, C.POINTER(SynthOptions), _fp, _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int,
                                              C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_fp), _fp, _fp, _fp, _fp, _fp]
+        lib.mpl_undistort_points.restype = C.c_int
+        lib.mpl_undistort_points.argtypes = [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp]
+        lib.mpl_prepare_inputs_ex.restype = C.c_int
+        lib.mpl_prepare_inputs_ex.argtypes = lib.mpl_prepare_inputs.argtypes[:3] + [_fp] + lib.mpl_prepare_inputs.argtypes[3:]
+        lib.mpl_synthesize_views_ex.restype = C.c_int
+        lib.mpl_synthesize_views_ex.argtypes = lib.mpl_synthesize_views.argtypes[:2] + [_fp] + lib.mpl_synthesize_views.argtypes[2:]
         lib.mpl_triangulate_rays.restype = C.c_int
         lib.mpl_triangulate_rays.argtypes = [C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_fp), C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp,
                                              _fp]

@@ -835,8 +835,23 @@ int mpl_prepare_inputs(const float* joints_px, const float* conf, const double* 
                        float img_w, float img_h, int normalize_inputs, int normalize_cameras, float* const* poses,
                        float* const* rays, float* const* centers, void* stream) {
     clear_stale_hip_error();
-    return launch_prepare_inputs(joints_px, conf, cams_dev, batch, views, joints, img_w, img_h, normalize_inputs,
+    return launch_prepare_inputs(joints_px, conf, cams_dev, nullptr, batch, views, joints, img_w, img_h, normalize_inputs,
                                  normalize_cameras, poses, rays, centers, (hipStream_t)stream);
+}
+
+int mpl_prepare_inputs_ex(const float* joints_px, const float* conf, const double* cams_dev, const double* dist_dev, int batch,
+                          int views, int joints, float img_w, float img_h, int normalize_inputs, int normalize_cameras,
+                          float* const* poses, float* const* rays, float* const* centers, void* stream) {
+    clear_stale_hip_error();
+    return launch_prepare_inputs(joints_px, conf, cams_dev, dist_dev, batch, views, joints, img_w, img_h, normalize_inputs,
+                                 normalize_cameras, poses, rays, centers, (hipStream_t)stream);
+}
+
+int mpl_undistort_points(const float* pixels, const double* cams_dev, const double* dist_dev, int batch, int views, int joints,
+                         int direction, float* out_pixels, unsigned char* out_valid, void* stream) {
+    clear_stale_hip_error();
+    return launch_undistort_points(pixels, cams_dev, dist_dev, batch, views, joints, direction, out_pixels, out_valid,
+                                   (hipStream_t)stream);
 }
 
 int mpl_decode_heatmaps(const void* const* heatmaps, int dtype, long long batch_stride, int batch, int views, int joints, int height,
@@ -888,8 +903,17 @@ int mpl_synthesize_views(const float* poses3d, const double* cams_dev, const mpl
                          int views, int joints, float* const* poses, float* const* rays, float* const* centers, float* target,
                          float* pixels, float* pixels_clean, float* depth, void* stream) {
     clear_stale_hip_error();
-    return launch_synthesize_views(poses3d, cams_dev, opt, conf, rotation_deg, translation, noise, missing_u, batch, views, joints,
-                                   poses, rays, centers, target, pixels, pixels_clean, depth, (hipStream_t)stream);
+    return launch_synthesize_views(poses3d, cams_dev, nullptr, opt, conf, rotation_deg, translation, noise, missing_u, batch, views,
+                                   joints, poses, rays, centers, target, pixels, pixels_clean, depth, (hipStream_t)stream);
+}
+
+int mpl_synthesize_views_ex(const float* poses3d, const double* cams_dev, const double* dist_dev, const mpl_synth_options* opt,
+                            const float* conf, const float* rotation_deg, const float* translation, const float* noise,
+                            const float* missing_u, int batch, int views, int joints, float* const* poses, float* const* rays,
+                            float* const* centers, float* target, float* pixels, float* pixels_clean, float* depth, void* stream) {
+    clear_stale_hip_error();
+    return launch_synthesize_views(poses3d, cams_dev, dist_dev, opt, conf, rotation_deg, translation, noise, missing_u, batch, views,
+                                   joints, poses, rays, centers, target, pixels, pixels_clean, depth, (hipStream_t)stream);
 }
 
 int mpl_triangulate_rays(const float* const* rays, const float* const* centers, const float* const* conf, int conf_stride, int batch,

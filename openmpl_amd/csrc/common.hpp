@@ -320,9 +320,14 @@ int launch_eval_accumulate(void* state, const mpl_eval_options* o, const float* 
 int eval_report_doubles(int n_sel, int n_groups);
 int launch_eval_report(const void* state, int n_sel, int n_groups, uint64_t skip_mask, double* rep, hipStream_t s);
 
-int launch_prepare_inputs(const float* px, const float* conf, const double* cams_dev, int B, int V, int J, float w, float h,
-                          int norm_in, int norm_cam, float* const* poses, float* const* rays, float* const* centers,
+// dist_dev: the (V,5) distortion table, or null for the pinhole kernel (mpl_prepare_inputs)
+int launch_prepare_inputs(const float* px, const float* conf, const double* cams_dev, const double* dist_dev, int B, int V, int J,
+                          float w, float h, int norm_in, int norm_cam, float* const* poses, float* const* rays, float* const* centers,
                           hipStream_t s);
+
+// distortion.hip: pixels through the lens model of views.hpp or back (mpl_undistort_points)
+int launch_undistort_points(const float* px, const double* cams_dev, const double* dist_dev, int B, int V, int J, int direction,
+                            float* out_px, unsigned char* out_valid, hipStream_t s);
 
 // heatmaps.hip: detector heatmaps -> pixels, confidences and (with cameras) model inputs (mpl_decode_heatmaps)
 int launch_decode_heatmaps(const void* const* heatmaps, int dtype, long long batch_stride, int B, int V, int J, int H, int W,
@@ -360,8 +365,8 @@ int launch_triangulate_robust(const float* const* rays, const float* const* cent
                               int V, int J, double threshold, double conf_threshold, int min_inliers, float* points,
                               float* residual, float* inliers, hipStream_t s);
 
-// synth.hip: model inputs synthesized from 3D poses (mpl_synthesize_views)
-int launch_synthesize_views(const float* poses3d, const double* cams_dev, const mpl_synth_options* opt, const float* conf,
+// synth.hip: model inputs synthesized from 3D poses (mpl_synthesize_views); dist_dev null: the pinhole kernel
+int launch_synthesize_views(const float* poses3d, const double* cams_dev, const double* dist_dev, const mpl_synth_options* opt, const float* conf,
                             const float* rotation_deg, const float* translation, const float* noise, const float* missing_u,
                             int B, int V, int J, float* const* poses, float* const* rays, float* const* centers, float* target,
                             float* pixels, float* pixels_clean, float* depth, hipStream_t s);

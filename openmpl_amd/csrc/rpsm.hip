@@ -84,14 +84,8 @@ __device__ __forceinline__ bool rpsm_project(const RpsmParams& p, int b, int v, 
     double xc, yc, zc;
     camera_coords(cam.c, X, Y, Z, xc, yc, zc);
     if (zc <= CAMERA_Z_MIN) return false;
-    const double y0 = xc / zc, y1 = yc / zc, r2 = y0 * y0 + y1 * y1;
-    double k1 = 0.0, k2 = 0.0, k3 = 0.0, p1 = 0.0, p2 = 0.0;         // zeros: the polynomial returns (y0, y1) bit for bit
-    if (p.dist) {
-        const double* d = p.dist + (size_t)v * 5;
-        k1 = d[0]; k2 = d[1]; k3 = d[2]; p1 = d[3]; p2 = d[4];
-    }
-    const double g = 1.0 + (k1 * r2 + k2 * (r2 * r2) + k3 * (r2 * r2 * r2)) + (2.0 * p1 * y1 + 2.0 * p2 * y0);
-    const double px = cam.fx() * (y0 * g + p2 * r2) + cam.cx(), py = cam.fy() * (y1 * g + p1 * r2) + cam.cy();
+    const Normalized yd = distort_normalized(xc / zc, yc / zc, distortion_of(p.dist, v));   // a null table: the pinhole, bit for bit
+    const double px = cam.fx() * yd.x + cam.cx(), py = cam.fy() * yd.y + cam.cy();
     const size_t bv = ((size_t)b * p.V + v) * 2;
     const double k = p.img_w / (200.0 * (double)p.scale[bv]);
     ux = ((px - (double)p.center[bv]) * k + p.img_w * 0.5) * (double)p.W / p.img_w;

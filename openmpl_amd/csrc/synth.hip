@@ -15,13 +15,18 @@
 //
 // The one deviation: a joint at z_cam <= 1e-9 (the reference divides anyway) gets confidence 0 and pixel (0,0) and skips the
 // noise, visibility and missing-joint steps; its ray and normalised pose follow from that pixel.
+//
+// With a distortion table (mpl_synthesize_views_ex) step 2 projects through the lens model of views.hpp, steps 3 to 5 act on the
+// distorted pixel, as a detector sees it, and step 6 is the arithmetic of mpl_prepare_inputs_ex: the ray goes through the
+// undistorted pixel, a pixel that is not invertible keeps its pinhole ray and gets confidence 0.
 #include "common.hpp"
 #include "detrng.hpp"
 #include "views.hpp"
 
 namespace mpl {
 
-struct SynthParams {
+struct SynthParams {                 // the pinhole launch: the kernel argument it has always had
+    static constexpr bool DIST = false;
     ViewOutputs out;
     mpl_synth_options o;
     const float* x3d;        // (B,J,3)
@@ -39,7 +44,15 @@ struct SynthParams {
     int B, V, J;
 };
 
-__global__ __launch_bounds__(256) void synthesize_views_kernel(const SynthParams p) {
+struct SynthLensParams : SynthParams {
+    static constexpr bool DIST = true;
+    const double* dist;      // device (V,5) distortion records
+};
+
+// P::DIST: step 2 projects through the lens and step 6 sends the ray through the undistorted pixel (views.hpp).  The lens comes with
+// its own argument type, so that the pinhole instantiation is the kernel it was, argument layout included
+template <class P>
+__global__ __launch_bounds__(256) void synthesize_views_kernel(const P p) {
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     const long long total = (long long)p.B * p.V * p.J;
     if (idx >= total) return;
@@ -77,8 +90,14 @@ __global__ __launch_bounds__(256) void synthesize_views_kernel(const SynthParams
     const bool front = zc > CAMERA_Z_MIN;
     double x = 0.0, y = 0.0, cf = 0.0;
     if (front) {
-        x = cam.fx() * xc / zc + cam.cx();
-        y = cam.fy() * yc / zc + cam.cy();
+        if constexpr (P::DIST) {       // px = fx (y0 g + p2 r2) + cx, the form of rpsm_project
+            const Normalized yd = distort_normalized(xc / zc, yc / zc, distortion_of(p.dist, v));
+            x = cam.fx() * yd.x + cam.cx();
+            y = cam.fy() * yd.y + cam.cy();
+        } else {
+            x = cam.fx() * xc / zc + cam.cx();
+            y = cam.fy() * yc / zc + cam.cy();
+        }
         cf = p.conf ? (double)p.conf[idx] : 1.0;
     }
     if (p.px_clean) {
@@ -137,8 +156,13 @@ __global__ __launch_bounds__(256) void synthesize_views_kernel(const SynthParams
     if (p.has_views) {
         asm volatile("" ::: "memory");
         const size_t ob = ((size_t)b * p.J + j) * 3;
-        prepare_point(c, x, y, (float)cf, o.img_w, o.img_h, o.normalize_inputs, o.normalize_cameras, p.out.poses[v] + ob, p.out.rays[v] + ob,
-                      j == 0 ? p.out.centers[v] + (size_t)b * 3 : nullptr);
+        if constexpr (P::DIST)
+            prepare_point_undistorted(c, distortion_of(p.dist, v), x, y, (float)cf, o.img_w, o.img_h, o.normalize_inputs,
+                                      o.normalize_cameras, p.out.poses[v] + ob, p.out.rays[v] + ob,
+                                      j == 0 ? p.out.centers[v] + (size_t)b * 3 : nullptr);
+        else
+            prepare_point(c, x, y, (float)cf, o.img_w, o.img_h, o.normalize_inputs, o.normalize_cameras, p.out.poses[v] + ob,
+                          p.out.rays[v] + ob, j == 0 ? p.out.centers[v] + (size_t)b * 3 : nullptr);
     }
 
     // 7. target
@@ -150,7 +174,7 @@ __global__ __launch_bounds__(256) void synthesize_views_kernel(const SynthParams
     }
 }
 
-int launch_synthesize_views(const float* poses3d, const double* cams_dev, const mpl_synth_options* opt, const float* conf,
+int launch_synthesize_views(const float* poses3d, const double* cams_dev, const double* dist_dev, const mpl_synth_options* opt, const float* conf,
                             const float* rotation_deg, const float* translation, const float* noise, const float* missing_u,
                             int B, int V, int J, float* const* poses, float* const* rays, float* const* centers, float* target,
                             float* pixels, float* pixels_clean, float* depth, hipStream_t s) {
@@ -164,14 +188,18 @@ int launch_synthesize_views(const float* poses3d, const double* cams_dev, const 
     if (!any && !target && !pixels && !pixels_clean && !depth) return MPL_E_INVALID;
     const long long total = (long long)B * V * J;
     if (total > (1ll << 36)) return MPL_E_UNSUPPORTED;
-    SynthParams p;
+    SynthLensParams p;
     if (const int rc = view_outputs_fill(p.out, poses, rays, centers, V, any)) return rc;
     p.o = *opt;
     p.x3d = poses3d; p.cams = cams_dev; p.conf = conf; p.rot_deg = rotation_deg; p.trans = translation; p.noise = noise;
     p.miss_u = missing_u; p.target = target; p.px = pixels; p.px_clean = pixels_clean; p.depth = depth;
-    p.has_views = any; p.B = B; p.V = V; p.J = J;
+    p.has_views = any; p.B = B; p.V = V; p.J = J; p.dist = dist_dev;
     ProfScope prof(MPL_K_FUSE_HEAD, s);
-    hipLaunchKernelGGL(synthesize_views_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, p);
+    if (dist_dev)
+        hipLaunchKernelGGL(synthesize_views_kernel<SynthLensParams>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, p);
+    else
+        hipLaunchKernelGGL(synthesize_views_kernel<SynthParams>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s,
+                           static_cast<const SynthParams&>(p));
     return hip_check_launch();
 }
 

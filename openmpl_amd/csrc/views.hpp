@@ -1,6 +1,6 @@
-// The three data formats of the pose utilities, each stated once: the camera record, the model-input lists and the heatmap table.
-// inputs.hip, heatmaps.hip, heatmap_render.hip, synth.hip and rpsm.hip read and write them through this header only (DESIGN.md
-// section 7).
+// The data formats of the pose utilities, each stated once: the camera record with its distortion record (the lens model and its
+// inverse), the model-input lists and the heatmap table.  inputs.hip, distortion.hip, heatmaps.hip, heatmap_render.hip, synth.hip and
+// rpsm.hip read and write them through this header only.
 #pragma once
 #include "common.hpp"
 
@@ -26,6 +26,74 @@ __device__ __forceinline__ void camera_coords(const double* c, double X, double 
     xc = cam.r(0, 0) * dx + cam.r(0, 1) * dy + cam.r(0, 2) * dz;
     yc = cam.r(1, 0) * dx + cam.r(1, 1) * dy + cam.r(1, 2) * dz;
     zc = cam.r(2, 0) * dx + cam.r(2, 1) * dy + cam.r(2, 2) * dz;
+}
+
+// ---- the distortion record: 5 doubles per view, k1 k2 k3 p1 p2; pack_distortion.  The lens model of the reference's
+// project_point_radial (lib/multiviews/cameras.py:22-46, the H36M form), stated once with its inverse.
+struct Distortion {
+    double k1, k2, k3, p1, p2;
+};
+
+// view v of a (V,5) table; a null table is the pinhole: zeros, under which distort_normalized returns (y0, y1) bit for bit
+__device__ __forceinline__ Distortion distortion_of(const double* dist, int v) {
+    Distortion d{0.0, 0.0, 0.0, 0.0, 0.0};
+    if (dist) {
+        const double* q = dist + (size_t)v * 5;
+        d.k1 = q[0]; d.k2 = q[1]; d.k3 = q[2]; d.p1 = q[3]; d.p2 = q[4];
+    }
+    return d;
+}
+
+struct Normalized {                          // a point in normalised camera coordinates, x_cam.xy / z
+    double x, y;
+};
+
+// a pinhole point -> the same after the lens: y (1 + radial + tangential) + (p2, p1) r2.  Contraction is the compiler's default, as
+// it was while rpsm_project held this expression; arguments and result go by value, which is what keeps rpsm's roundings in place
+__device__ __forceinline__ Normalized distort_normalized(double y0, double y1, Distortion d) {
+    const double r2 = y0 * y0 + y1 * y1;
+    const double g = 1.0 + (d.k1 * r2 + d.k2 * (r2 * r2) + d.k3 * (r2 * r2 * r2)) + (2.0 * d.p1 * y1 + 2.0 * d.p2 * y0);
+    return Normalized{y0 * g + d.p2 * r2, y1 * g + d.p1 * r2};
+}
+
+constexpr int UNDISTORT_MAX_ITER = 20;       // a guard: the coefficient sets of the tests take at most 4 on a centred subject
+constexpr double UNDISTORT_TOL = 1e-14;
+
+// The inverse: Newton from y = y_d with the analytic Jacobian.  false (not invertible): an iterate with det J <= 0 -- the point lies
+// beyond the fold of the polynomial --, a non-finite value, or no step below UNDISTORT_TOL * max(1, |y|_inf) within the cap; y0, y1
+// then hold the last iterate.  With zero coefficients the first residual is exactly 0 and y = y_d bit for bit.
+__device__ __forceinline__ bool undistort_normalized(double yd0, double yd1, Distortion d, double& y0, double& y1) {
+    y0 = yd0;
+    y1 = yd1;
+    for (int it = 0; it < UNDISTORT_MAX_ITER; ++it) {
+        const double r2 = y0 * y0 + y1 * y1;
+        const double g = 1.0 + (d.k1 * r2 + d.k2 * (r2 * r2) + d.k3 * (r2 * r2 * r2)) + (2.0 * d.p1 * y1 + 2.0 * d.p2 * y0);
+        const double gr = d.k1 + 2.0 * d.k2 * r2 + 3.0 * d.k3 * (r2 * r2);                   // dg / dr2
+        const double g0 = 2.0 * (gr * y0 + d.p2), g1 = 2.0 * (gr * y1 + d.p1);               // dg / dy
+        const double f0 = (y0 * g + d.p2 * r2) - yd0, f1 = (y1 * g + d.p1 * r2) - yd1;
+        const double j00 = g + y0 * g0 + 2.0 * d.p2 * y0, j01 = y0 * g1 + 2.0 * d.p2 * y1;
+        const double j10 = y1 * g0 + 2.0 * d.p1 * y0, j11 = g + y1 * g1 + 2.0 * d.p1 * y1;
+        const double det = j00 * j11 - j01 * j10;
+        if (!(det > 0.0)) return false;
+        const double s0 = (j11 * f0 - j01 * f1) / det, s1 = (j00 * f1 - j10 * f0) / det;
+        y0 -= s0;
+        y1 -= s1;
+        if (!(isfinite(y0) && isfinite(y1))) return false;
+        if (fmax(fabs(s0), fabs(s1)) <= UNDISTORT_TOL * fmax(1.0, fmax(fabs(y0), fabs(y1)))) return true;
+    }
+    return false;
+}
+
+// The observed pixel (x, y) of view c -> the pixel a pinhole camera would have seen, (x + fx D0, y + fy D1) with D = y_u - y_d in
+// normalised coordinates: zero coefficients give D = 0 and the input.  false: not invertible, (xu, yu) is then not to be used.
+__device__ __forceinline__ bool undistort_pixel(const double* c, Distortion d, double x, double y, double& xu, double& yu) {
+    const Camera cam{c};
+    const double yd0 = (x - cam.cx()) / cam.fx(), yd1 = (y - cam.cy()) / cam.fy();
+    double y0, y1;
+    const bool ok = undistort_normalized(yd0, yd1, d, y0, y1);
+    xu = x + cam.fx() * (y0 - yd0);
+    yu = y + cam.fy() * (y1 - yd1);
+    return ok;
 }
 
 // The arithmetic of input preparation for one (sample, view, joint).  Reference: inputs.hip.
@@ -55,6 +123,29 @@ __device__ __forceinline__ void prepare_point(const double* c, double x, double 
 #pragma unroll
         for (int d = 0; d < 3; ++d) co[d] = (float)cam.t(d);
     }
+}
+
+// The same under a lens: the ray is that of prepare_point on the undistorted pixel, whose poses are dropped; poses hold the observed
+// pixel, normalised as prepare_point does, and the confidence.  A pixel that is not invertible keeps its pinhole ray and gets
+// confidence 0, like a missing joint: every geometric consumer then drops the view.  prepare_point itself stays as it is, so that
+// the pinhole kernels (decode_kernel among them) keep their code.
+__device__ __forceinline__ void prepare_point_undistorted(const double* c, Distortion d, double x, double y, float cf, double w,
+                                                          double h, int norm_in, int norm_cam, float* po, float* ro, float* co) {
+    double xu, yu;
+    if (!undistort_pixel(c, d, x, y, xu, yu)) {
+        xu = x;
+        yu = y;
+        cf = 0.0f;
+    }
+    float dropped[3];
+    prepare_point(c, xu, yu, cf, w, h, norm_in, norm_cam, dropped, ro, co);
+    if (norm_in) {
+        x = (x / w) * 2.0 - 1.0;
+        y = (y / w) * 2.0 - h / w;
+    }
+    po[0] = (float)x;
+    po[1] = (float)y;
+    po[2] = cf;
 }
 
 // ---- the model-input lists: poses, rays, centers, V tensors (B,J,3), (B,J,3), (B,1,3) each; what mpl_forward consumes

@@ -125,6 +125,25 @@ def triangulate_rays_robust(rays: Sequence[torch.Tensor], centers: Sequence[torc
     return points, residual, inliers
 
 
+def triangulate_pixels(pixels: torch.Tensor, conf: Optional[torch.Tensor], cams: torch.Tensor,
+                       image_size: Optional[Tuple[float, float]] = None, distortion: Optional[torch.Tensor] = None,
+                       threshold: Optional[float] = None, conf_threshold: Optional[float] = None
+                       ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The call shape of the reference's triangulate_poses(camera_params, poses2d, confs) (lib/multiviews/triangulate.py:59-115) for
+    a batch: pixels (B,V,J,2) float32 GPU, conf (B,V,J) or None, cams (V,16) float64 (pack_cameras), distortion (V,5) float64
+    (pack_distortion) or None -> (points (B,J,3), residual (B,J), inliers (B,V,J)).
+
+    A thin wrapper, no kernel of its own: prepare_inputs(pixels, conf, cams, image_size, False, False, distortion=) -- the rays go
+    through the undistorted pixels, and a joint whose pixel is not invertible takes no part in that view -- then
+    triangulate_rays_robust(rays, centers, poses as the confidences, threshold, conf_threshold), which with both stages off is
+    triangulate_rays.  Without normalisation image_size is not looked at; it defaults to (1, 1).  Where the reference hands its
+    coefficients to pymvg's OpenCV model, this inverts the model the projection uses (include/mpl_hip.h)."""
+    from .inputs import prepare_inputs
+    poses, rays, centers = prepare_inputs(pixels, conf, cams, (1.0, 1.0) if image_size is None else image_size, False, False,
+                                          distortion=distortion)
+    return triangulate_rays_robust(rays, centers, poses, threshold=threshold, conf_threshold=conf_threshold)
+
+
 def _epipolar(rays, centers, conf, weight, threshold):
     rays, centers, conf, weight, stride, B, V, J = _lines(rays, centers, conf, weight)
     if V < 2:

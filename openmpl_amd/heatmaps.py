@@ -16,6 +16,7 @@ import torch
 
 from . import cabi, detrng
 from ._marshal import HM_DTYPES, dtypes_and_devices, heatmap_shapes, heatmap_table, named_shapes, ptr, table, view_lists
+from .inputs import prepare_inputs
 
 
 class DecodedHeatmaps(NamedTuple):
@@ -27,14 +28,15 @@ class DecodedHeatmaps(NamedTuple):
     centers: Optional[List[torch.Tensor]]     # V x (B,1,3)
 
 
-def _check(heatmaps, center, scale, cams, image_size):
+def _check(heatmaps, center, scale, cams, image_size, distortion=None):
     """Shapes first, then dtypes, then devices, as geometry._lines does -> (views, B, V, J, H, W), the views being one (B,J,H,W)
     tensor each or None for the (B,V,J,H,W) tensor."""
     views, maps, B, V, J, H, W = heatmap_shapes(heatmaps, RuntimeError)
     if (center is None) != (scale is None):
         raise RuntimeError("center and scale go together (got only %s)" % ("center" if scale is None else "scale"))
     named = [(n, t, s, d) for n, t, s, d in (("center", center, (B, V, 2), torch.float32), ("scale", scale, (B, V, 2), torch.float32),
-                                             ("cams", cams, (V, 16), torch.float64)) if t is not None]
+                                             ("cams", cams, (V, 16), torch.float64), ("distortion", distortion, (V, 5), torch.float64))
+             if t is not None]
     named_shapes(named, RuntimeError)
     if cams is not None:
         if image_size is None:
@@ -52,7 +54,7 @@ def decode_heatmaps(heatmaps: Union[torch.Tensor, Sequence[torch.Tensor]], cente
                     scale: Optional[torch.Tensor] = None, *, post_process: bool = False, cams: Optional[torch.Tensor] = None,
                     image_size: Optional[Tuple[float, float]] = None, normalize_inputs: bool = True, normalize_cameras: bool = True,
                     return_coords: bool = False, subpixel: Optional[str] = None, radius: int = 2,
-                    threshold: float = 1e-6) -> DecodedHeatmaps:
+                    threshold: float = 1e-6, distortion: Optional[torch.Tensor] = None) -> DecodedHeatmaps:
     """heatmaps: a list of V (B,J,H,W) tensors (what a 2D backbone returns per view) or one (B,V,J,H,W) tensor; float32, float16 or
     bfloat16 on a GPU.  A tensor whose (J,H,W) block is dense is read in place, whatever its batch stride; nothing is copied to
     change a layout.  Per heatmap, as get_final_preds does:
@@ -77,7 +79,15 @@ def decode_heatmaps(heatmaps: Union[torch.Tensor, Sequence[torch.Tensor]], cente
        peak, of the values above `threshold` in the window of `radius` (1..8) cells about it, cells outside the map counting 0; the
        sum of the weights gets 2.22e-16 added.  More robust under noise, biased towards the peak on clean maps.
 
-    Returns DecodedHeatmaps(pixels, conf, coords, poses, rays, centers); what was not asked for is None.  One launch."""
+    distortion (V,5) float64 (pack_distortion), with cams: the decoded pixels are what the lens showed the detector, so the rays
+    must go through the undistorted pixels.  The plain decode is then followed by prepare_inputs(pixels, conf, cams, image_size,
+    normalize_inputs, normalize_cameras, distortion=) -- TWO launches, and bitwise that composition; the Newton inverse is kept
+    out of the decode kernel, whose finishing lane is already its longest path.
+
+    Returns DecodedHeatmaps(pixels, conf, coords, poses, rays, centers); what was not asked for is None.  One launch, two with
+    distortion."""
+    if distortion is not None and cams is None:
+        raise RuntimeError("distortion needs cams: it only changes the rays")
     if subpixel not in cabi.REFINE:
         raise RuntimeError("subpixel must be None, 'gaussian' or 'centroid', got %r" % (subpixel,))
     if subpixel is not None and post_process:
@@ -87,7 +97,7 @@ def decode_heatmaps(heatmaps: Union[torch.Tensor, Sequence[torch.Tensor]], cente
             raise RuntimeError("radius must be an integer from 1 to 8, got %r" % (radius,))
         if not float(threshold) == float(threshold):
             raise RuntimeError("threshold must be a number, got %r" % (threshold,))
-    views, B, V, J, H, W = _check(heatmaps, center, scale, cams, image_size)
+    views, B, V, J, H, W = _check(heatmaps, center, scale, cams, image_size, distortion)
     keep, hm, stride, dtype = heatmap_table(heatmaps, views, B, V, J, H, W)
     dev = keep[0].device
     if center is not None:
@@ -97,16 +107,19 @@ def decode_heatmaps(heatmaps: Union[torch.Tensor, Sequence[torch.Tensor]], cente
     coords = torch.empty((B, V, J, 2), dtype=torch.float32, device=dev) if return_coords else None
     poses = rays = centers = None
     w = h = 0.0
-    if cams is not None:
-        cams = cams.contiguous()
+    fused = cams if distortion is None else None          # the decode kernel writes the model inputs itself
+    if fused is not None:
+        fused = fused.contiguous()
         w, h = float(image_size[0]), float(image_size[1])
         poses, rays, centers = view_lists(B, V, J, dev)
     args = (hm, dtype, stride, B, V, J, H, W, int(bool(post_process)), ptr(center), ptr(scale), pixels.data_ptr(), conf.data_ptr(),
-            ptr(coords), ptr(cams), w, h, int(bool(normalize_inputs)), int(bool(normalize_cameras)), table(poses), table(rays), table(centers))
+            ptr(coords), ptr(fused), w, h, int(bool(normalize_inputs)), int(bool(normalize_cameras)), table(poses), table(rays), table(centers))
     if subpixel is None:
         cabi.launch("decode_heatmaps", dev, *args)
     else:
         cabi.launch("decode_heatmaps_ex", dev, *args, cabi.REFINE[subpixel], int(radius), float(threshold))
+    if distortion is not None:
+        poses, rays, centers = prepare_inputs(pixels, conf, cams, image_size, normalize_inputs, normalize_cameras, distortion=distortion)
     return DecodedHeatmaps(pixels, conf, coords, poses, rays, centers)
 
 

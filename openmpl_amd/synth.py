@@ -18,6 +18,7 @@ import torch
 
 from . import cabi, detrng
 from ._marshal import ptr, table, vec3, view_lists
+from .inputs import check_distortion
 
 SynthViews = namedtuple("SynthViews", "poses rays centers target pixels pixels_clean")
 
@@ -58,7 +59,8 @@ def synthesize_views(poses3d: torch.Tensor, cams: torch.Tensor, image_size: Tupl
                      conf: Optional[torch.Tensor] = None, normalize_inputs: bool = True, normalize_cameras: bool = True,
                      target_scale=None, target_offset=None, rotation_deg: Optional[torch.Tensor] = None,
                      translation: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
-                     missing_u: Optional[torch.Tensor] = None, return_pixels: bool = False) -> SynthViews:
+                     missing_u: Optional[torch.Tensor] = None, return_pixels: bool = False,
+                     distortion: Optional[torch.Tensor] = None) -> SynthViews:
     """poses3d (B,J,3) float32 GPU (world units), cams (V,16) float64 GPU (pack_cameras), image_size (w, h) in pixels.
 
     rotate: turn every pose about the world z axis by 360 * u degrees; room = (min_x, max_x, min_y, max_y): add
@@ -69,6 +71,10 @@ def synthesize_views(poses3d: torch.Tensor, cams: torch.Tensor, image_size: Tupl
     (default 1).  rotation_deg (B), translation (B,3), noise (B,V,J,2) and missing_u (B,V,J) replace the stream of their step.
     target = (placed pose - target_offset) / target_scale per axis: with the same two vectors as scale / offset of
     PoseEvaluator.update the evaluator scores in world units.
+    distortion (V,5) float64 (pack_distortion): the projection goes through the lens (project_point_radial,
+    lib/multiviews/cameras.py:22-46); pixels_clean, the noise, the visibility step and the missing joints act on distorted pixels, as
+    a detector sees them; the rays go through the undistorted pixels, exactly as prepare_inputs(distortion=) builds them.  Without
+    it the launch and the bits are what they always were; zero coefficients agree with that to float64 rounding, not bitwise.
 
     Returns SynthViews(poses, rays, centers, target, pixels, pixels_clean): the first three are the lists of V tensors (B,J,3),
     (B,J,3), (B,1,3) that model(poses, rays=, centers=) takes; target (B,J,3); pixels (after the missing-joint step) and
@@ -76,6 +82,7 @@ def synthesize_views(poses3d: torch.Tensor, cams: torch.Tensor, image_size: Tupl
     Runs on the current stream and does not synchronise."""
     B, V, J = _check_scene(poses3d, cams, "synthesize_views")
     dev = poses3d.device
+    distortion = check_distortion(distortion, V, dev)
     if penalize not in cabi.SYNTH_PENALIZE:
         raise RuntimeError("penalize must be one of %s, got %r" % (", ".join(sorted(cabi.SYNTH_PENALIZE)), penalize))
     w, h = float(image_size[0]), float(image_size[1])
@@ -111,23 +118,35 @@ def synthesize_views(poses3d: torch.Tensor, cams: torch.Tensor, image_size: Tupl
     target = torch.empty((B, J, 3), dtype=torch.float32, device=dev)
     pixels = torch.empty((B, V, J, 2), dtype=torch.float32, device=dev) if return_pixels else None
     clean = torch.empty((B, V, J, 2), dtype=torch.float32, device=dev) if return_pixels else None
-    cabi.launch("synthesize_views", dev, poses3d.data_ptr(), cams.data_ptr(), C.byref(o), ptr(conf), ptr(rotation_deg), ptr(translation),
-                ptr(noise), ptr(missing_u), B, V, J, table(poses), table(rays), table(centers), target.data_ptr(), ptr(pixels), ptr(clean), None)
+    _launch(dev, distortion, poses3d.data_ptr(), cams.data_ptr(), C.byref(o), ptr(conf), ptr(rotation_deg), ptr(translation),
+            ptr(noise), ptr(missing_u), B, V, J, table(poses), table(rays), table(centers), target.data_ptr(), ptr(pixels), ptr(clean), None)
     return SynthViews(poses, rays, centers, target, pixels, clean)
 
 
-def project_points(points3d: torch.Tensor, cams: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+def _launch(dev, distortion, poses3d, cams, *rest):
+    """mpl_synthesize_views, or with a distortion table its _ex form"""
+    if distortion is None:
+        cabi.launch("synthesize_views", dev, poses3d, cams, *rest)
+    else:
+        cabi.launch("synthesize_views_ex", dev, poses3d, cams, distortion.data_ptr(), *rest)
+
+
+def project_points(points3d: torch.Tensor, cams: torch.Tensor, distortion: Optional[torch.Tensor] = None
+                   ) -> Tuple[torch.Tensor, torch.Tensor]:
     """points3d (B,J,3) float32 GPU, cams (V,16) float64 GPU -> (pixels (B,V,J,2), depth (B,V,J)): x_cam = R (X - t),
     pixel = (fx x / z + cx, fy y / z + cy), depth = z.  The same launch as synthesize_views with every perturbation off: the
-    reprojection that scores a predicted pose against detections.  A point at depth <= 1e-9 gets pixel (0,0)."""
+    reprojection that scores a predicted pose against detections.  A point at depth <= 1e-9 gets pixel (0,0).
+    distortion (V,5) float64 (pack_distortion): the pixel is f y_d + c, y_d the lens polynomial of y = x_cam.xy / z -- the
+    reference's project_pose (lib/multiviews/cameras.py:22-51)."""
     B, V, J = _check_scene(points3d, cams, "project_points")
     dev = points3d.device
+    distortion = check_distortion(distortion, V, dev)
     o = cabi.SynthOptions()
     o.img_w = o.img_h = 1.0
     o.target_scale[:] = [1.0] * 3
     points3d, cams = points3d.contiguous(), cams.contiguous()
     pixels = torch.empty((B, V, J, 2), dtype=torch.float32, device=dev)
     depth = torch.empty((B, V, J), dtype=torch.float32, device=dev)
-    cabi.launch("synthesize_views", dev, points3d.data_ptr(), cams.data_ptr(), C.byref(o), None, None, None, None, None, B, V, J, None, None,
-                None, None, None, pixels.data_ptr(), depth.data_ptr())
+    _launch(dev, distortion, points3d.data_ptr(), cams.data_ptr(), C.byref(o), None, None, None, None, None, B, V, J, None, None,
+            None, None, None, pixels.data_ptr(), depth.data_ptr())
     return pixels, depth
