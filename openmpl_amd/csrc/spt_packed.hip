@@ -162,6 +162,108 @@ int launch_spt_pack(const mpl_block_weights* bw_host, unsigned short* dst, int f
 
 size_t spt_pack_bytes() { return SPT_PACK_BYTES; }
 
+template <int N>
+struct SptInt { static constexpr int value = N; };
+
+// One Linear phase of ONE wave as straight-line code: the wave's units u = NCT m + n (row tile m, column tile n) of the phase's
+// (m, n) list are LO .. HI - 1, compile-time (SPT_BY_WAVE below: one instantiation per wave of the workgroup), so every row tile,
+// column range and LDS offset is a constant and nothing is left of the unit loop.  KS k steps of 32 (fc2: 2); LN: the A fragment
+// is the normalised row of X (qkv's ln_frag), else a plain operand row (stride AST) that already carries its static scale; GELU:
+// D = gelu(y) times the scale of the fc2 operand (stride DST), else the residual D += y.  An A fragment is formed once per row
+// tile the wave touches; the operand rows -- and the residual rows -- of the NEXT row tile are read before the products of this
+// one.  The product chain of a unit is mfma3 per k step, one unit after the other: chains of neighbouring column tiles
+// interleaved product by product in the SOURCE gave other bits in the 4-sequence form on the device (HISTORY.md), so the order
+// among independent chains is left to the compiler.
+template <int KS, bool LN, bool GELU, int NCT, int AST, int DST, int LO, int HI>
+__device__ __forceinline__ void spt_linear_role(const float* A, float* D, const char* wsec, const float* par, int col0, float hs,
+                                                int lane) {
+    if constexpr (HI > LO) {
+        constexpr int M0 = LO / NCT, NM = (HI - 1) / NCT - M0 + 1;
+        const int li = lane & 15, kq = lane >> 4;
+        sf16x8 w[NCT][KS][2];
+        float4 bc[NCT], sc[NCT];               // c_n and sc_n of this lane's columns
+#pragma unroll
+        for (int n = 0; n < NCT; ++n) {
+            if (HI - LO < NCT && (n - LO % NCT + NCT) % NCT >= HI - LO) continue;     // a column tile this wave never meets
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) spt_load_unit(wsec, n * KS + ks, lane, w[n][ks]);
+            bc[n] = ::mpl::ld4(par + col0 + 16 * n + 4 * kq);
+            sc[n] = ::mpl::ld4(par + SPT_NCOL + col0 + 16 * n + 4 * kq);
+        }
+        const float* a0 = A + li * AST + 8 * kq;
+        float* d0 = D + li * DST + 4 * kq;
+        float4 raw[KS][2], res[NCT];
+        auto read_tile = [&](int i) {          // operand rows and residual rows of the wave's i-th row tile
+            const int m = M0 + i;
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+                raw[ks][0] = ::mpl::ld4(a0 + m * 16 * AST + 32 * ks);
+                raw[ks][1] = ::mpl::ld4(a0 + m * 16 * AST + 32 * ks + 4);
+            }
+            if (!GELU) {
+#pragma unroll
+                for (int n = 0; n < NCT; ++n)
+                    if (NCT * m + n >= LO && NCT * m + n < HI) res[n] = ::mpl::ld4(d0 + m * 16 * DST + 16 * n);
+            }
+        };
+        read_tile(0);
+#pragma unroll
+        for (int i = 0; i < NM; ++i) {
+            const int m = M0 + i;
+            sf16x8 ah[KS], al[KS];
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+                if (LN) {
+                    spt_ln_split(raw[ks][0], raw[ks][1], ah[ks], al[ks]);
+                } else {
+                    const float4 x0 = raw[ks][0], x1 = raw[ks][1];
+                    const float y[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
+                    spt_split2(y, ah[ks], al[ks]);
+                }
+            }
+            float4 x[NCT];
+#pragma unroll
+            for (int n = 0; n < NCT; ++n) x[n] = res[n];
+            if (i + 1 < NM) read_tile(i + 1);
+            f32x4 c[NCT];
+#pragma unroll
+            for (int n = 0; n < NCT; ++n) c[n] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int n = 0; n < NCT; ++n) {
+                if (NCT * m + n < LO || NCT * m + n >= HI) continue;
+#pragma unroll
+                for (int ks = 0; ks < KS; ++ks) c[n] = mfma3(w[n][ks], ah[ks], al[ks], c[n]);
+            }
+#pragma unroll
+            for (int n = 0; n < NCT; ++n) {
+                if (NCT * m + n < LO || NCT * m + n >= HI) continue;
+                float* dd = d0 + m * 16 * DST + 16 * n;
+                if (GELU)
+                    st4(dd, float4{gelu_as_scaled(fmaf(c[n][0], sc[n].x, bc[n].x), hs), gelu_as_scaled(fmaf(c[n][1], sc[n].y, bc[n].y), hs),
+                                   gelu_as_scaled(fmaf(c[n][2], sc[n].z, bc[n].z), hs), gelu_as_scaled(fmaf(c[n][3], sc[n].w, bc[n].w), hs)});
+                else
+                    st4(dd, float4{x[n].x + fmaf(c[n][0], sc[n].x, bc[n].x), x[n].y + fmaf(c[n][1], sc[n].y, bc[n].y),
+                                   x[n].z + fmaf(c[n][2], sc[n].z, bc[n].z), x[n].w + fmaf(c[n][3], sc[n].w, bc[n].w)});
+            }
+        }
+    }
+}
+// the phase of wave `wv` (scalar): units NU * wv / NWAVE .. NU * (wv + 1) / NWAVE - 1 of the NU = MTS * NCT of the workgroup
+#define SPT_ROLE(W, MTS, KS, LN, GELU, NCT, AST, DST, ...) \
+    spt_linear_role<KS, LN, GELU, NCT, AST, DST, ((MTS) * (NCT) * (W)) / NWAVE, ((MTS) * (NCT) * ((W) + 1)) / NWAVE>(__VA_ARGS__)
+#define SPT_BY_WAVE(wv, ...)                          \
+    switch (wv) {                                     \
+        case 0: SPT_ROLE(0, __VA_ARGS__); break;      \
+        case 1: SPT_ROLE(1, __VA_ARGS__); break;      \
+        case 2: SPT_ROLE(2, __VA_ARGS__); break;      \
+        case 3: SPT_ROLE(3, __VA_ARGS__); break;      \
+        case 4: SPT_ROLE(4, __VA_ARGS__); break;      \
+        case 5: SPT_ROLE(5, __VA_ARGS__); break;      \
+        case 6: SPT_ROLE(6, __VA_ARGS__); break;      \
+        default: SPT_ROLE(7, __VA_ARGS__); break;     \
+    }
+
+
 // SS = sequences per workgroup (16, 8, 4, 2 or 1): rows = joint * SS + sequence, 17 SS of them in MTS row tiles.  A launch of few
 // sequences takes as few per workgroup as keep it within one workgroup per CU (launch_spt): the kernel's time is VALU work per ROW
 // TILE, so 4 sequences per workgroup walk 5 tiles instead of 17.  The arithmetic of a row does not depend on SS (the matrix
@@ -232,13 +334,6 @@ __global__ __launch_bounds__(NTHR, 1) void spt3_kernel(const SptParams p) {
         const float* xr = X + (m * 16 + li) * XS + 8 * kq;
         spt_ln_split(::mpl::ld4(xr), ::mpl::ld4(xr + 4), ah, al);
     };
-    // plain A fragment: the producer already applied the static scale of the operand (attention output, GELU output)
-    auto raw_frag = [&](const float* rowp, sf16x8& ah, sf16x8& al) {
-        const float4 x0 = ::mpl::ld4(rowp), x1 = ::mpl::ld4(rowp + 4);
-        const float y[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
-        spt_split2(y, ah, al);
-    };
-
     for (int app = 0; app < p.n_apps; ++app) {
         const bool weighted = (p.sched[app] & 0x80) != 0;
         bw = set.blocks[p.sched[app] & 0x7f];
@@ -294,16 +389,18 @@ __global__ __launch_bounds__(NTHR, 1) void spt3_kernel(const SptParams p) {
             // Scores in the exp2 domain (the q columns carry hd^-0.5 log2 e = 0.5 log2 e from their epilogue multiplier), the
             // probabilities stay unnormalised until the output row is complete; the output leaves with the static scale of the
             // proj operand (par[448], a power of two).
-            if (!(p.abl & 1)) {
+            // A wave whose last tile part + 4 (NT - 1) does not exist (SS = 16: every part but 0) runs the phase over NT - 1 tiles.
+            auto attention = [&](auto live_tiles) {
+                constexpr int NL = decltype(live_tiles)::value;
                 const int h = 4 * hg + kq;
-                float sc[NT][SJ];
+                float sc[NL][SJ];
 #pragma unroll
                 for (int jp = 0; jp < SJ / 2; ++jp) {
                     const float4 k01 = ::mpl::ld4(Kb + (((jp * 2) * SH + h) * SS + sl) * 4);        // x_j x_j+1 y_j y_j+1
                     const float4 k23 = ::mpl::ld4(Kb + (((jp * 2 + 1) * SH + h) * SS + sl) * 4);    // z_j z_j+1 w_j w_j+1
                     const f32x2 kx = {k01.x, k01.y}, ky = {k01.z, k01.w}, kz = {k23.x, k23.y}, kw = {k23.z, k23.w};
 #pragma unroll
-                    for (int t = 0; t < NT; ++t) {
+                    for (int t = 0; t < NL; ++t) {
                         const f32x2 qx = {q[t].x, q[t].x}, qy = {q[t].y, q[t].y}, qz = {q[t].z, q[t].z}, qw = {q[t].w, q[t].w};
                         f32x2 s2 = qx * kx;
                         s2 = __builtin_elementwise_fma(qy, ky, s2);
@@ -316,13 +413,23 @@ __global__ __launch_bounds__(NTHR, 1) void spt3_kernel(const SptParams p) {
                 {
                     const float4 k = ::mpl::ld4(Kb + (SJ - 1) * SH * SS * 4 + (h * SS + sl) * 4);
 #pragma unroll
-                    for (int t = 0; t < NT; ++t)
+                    for (int t = 0; t < NL; ++t)
                         sc[t][SJ - 1] = fmaf(q[t].w, k.w, fmaf(q[t].z, k.z, fmaf(q[t].y, k.y, q[t].x * k.x)));
                 }
                 const float s_att = par[2 * SPT_NCOL];
-                float inv[NT];
+                // Confidence of this lane's row in tile t = 0 (the weighted application scales the query rows by it), rebuilt
+                // from the lane index where it is needed: as a loop invariant the address -- one per tile, as it was written
+                // before -- is kept in registers across every phase of every application, which the 16-sequence form paid for
+                // with scratch.  The empty asm makes the lane index a value of this iteration.
+                const float* conf0 = nullptr;
+                if (weighted) {
+                    int l16 = li;
+                    asm volatile("" : "+v"(l16));
+                    conf0 = pose + ((size_t)(b0 + l16 % SS) * SJ + (16 * part + l16) / SS) * 3 + 2;
+                }
+                float inv[NL];
 #pragma unroll
-                for (int t = 0; t < NT; ++t) {
+                for (int t = 0; t < NL; ++t) {
                     float mx = sc[t][0];
 #pragma unroll
                     for (int j = 1; j < SJ; ++j) mx = fmaxf(mx, sc[t][j]);
@@ -334,18 +441,19 @@ __global__ __launch_bounds__(NTHR, 1) void spt3_kernel(const SptParams p) {
                     }
                     inv[t] = __builtin_amdgcn_rcpf(l) * s_att;              // v_rcp_f32 (1 ulp)
                     if (weighted) {  // attn * conf_weights.unsqueeze(1) after softmax (:61-62): scales the query row
+                        // row r = 16 (part + 4 t) + li is joint r / SS = (16 part + li) / SS + (64 / SS) t: a constant offset per tile
                         const int b = b0 + sl, r = 16 * (part + 4 * t) + li;
-                        inv[t] *= (b < p.B && r < RLIVE) ? pose[((size_t)b * SJ + r / SS) * 3 + 2] : 0.f;
+                        inv[t] *= (b < p.B && r < RLIVE) ? conf0[3 * (64 / SS) * t] : 0.f;
                     }
                 }
-                float4 o[NT];
+                float4 o[NL];
 #pragma unroll
-                for (int t = 0; t < NT; ++t) o[t] = float4{0.f, 0.f, 0.f, 0.f};
+                for (int t = 0; t < NL; ++t) o[t] = float4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int j = 0; j < SJ; ++j) {
                     const float4 v = ::mpl::ld4(Vb + ((j * SH + h) * SS + sl) * 4);
 #pragma unroll
-                    for (int t = 0; t < NT; ++t) {
+                    for (int t = 0; t < NL; ++t) {
                         const float pj = sc[t][j];
                         o[t].x = fmaf(pj, v.x, o[t].x);
                         o[t].y = fmaf(pj, v.y, o[t].y);
@@ -354,7 +462,7 @@ __global__ __launch_bounds__(NTHR, 1) void spt3_kernel(const SptParams p) {
                     }
                 }
 #pragma unroll
-                for (int t = 0; t < NT; ++t) {
+                for (int t = 0; t < NL; ++t) {
                     o[t] = float4{o[t].x * inv[t], o[t].y * inv[t], o[t].z * inv[t], o[t].w * inv[t]};
                     // the confidence weights are data (reference :61-62 multiplies the softmax rows by whatever `conf` it is
                     // given): only with them can the operand leave the window its static, data-free scale assumes.  That is
@@ -371,66 +479,22 @@ __global__ __launch_bounds__(NTHR, 1) void spt3_kernel(const SptParams p) {
                     }
                 }
 #pragma unroll
-                for (int t = 0; t < NT; ++t)
-                    if (part + 4 * t < MTS) st4(ATT + ((part + 4 * t) * 16 + li) * ATS + 4 * h, o[t]);
+                for (int t = 0; t < NL; ++t) st4(ATT + ((part + 4 * t) * 16 + li) * ATS + 4 * h, o[t]);
+            };
+            if (!(p.abl & 1)) {
+                if (part + 4 * (NT - 1) < MTS) attention(SptInt<NT>{});
+                else if (NT > 1) attention(SptInt<(NT > 1 ? NT - 1 : 1)>{});
             }
         }
         phase_sync();
         // ---------------- X += attn_out . Wproj^T + b : 17 x 2 tiles, dealt as contiguous ranges of the (m, n) list
-        {
-            stage_w(R_F1, pack, SPT_PACK_FC1, 8);       // fc1 weights into the dead K tile
-            sf16x8 wp[2][2];
-            float4 bp[2], sp[2];
-#pragma unroll
-            for (int n = 0; n < 2; ++n) {
-                load_w(S_W, n, wp[n]);
-                bp[n] = ::mpl::ld4(par + SPT_C_PROJ + 16 * n + 4 * kq);
-                sp[n] = ::mpl::ld4(par + SPT_NCOL + SPT_C_PROJ + 16 * n + 4 * kq);
-            }
-            const int lo = (MTS * 2 * wave) / NWAVE, hi = (MTS * 2 * (wave + 1)) / NWAVE;
-            for (int m = lo >> 1; m <= ((hi - 1) >> 1) && !(p.abl & 32); ++m) {
-                sf16x8 ah, al;
-                raw_frag(ATT + (m * 16 + li) * ATS + 8 * kq, ah, al);
-#pragma unroll
-                for (int n = 0; n < 2; ++n) {
-                    const int u = 2 * m + n;
-                    if (u < lo || u >= hi) continue;
-                    const f32x4 c = mfma3(wp[n], ah, al, f32x4{0.f, 0.f, 0.f, 0.f});
-                    float* xd = X + (m * 16 + li) * XS + 16 * n + 4 * kq;
-                    const float4 x = ::mpl::ld4(xd);
-                    st4(xd, float4{x.x + fmaf(c[0], sp[n].x, bp[n].x), x.y + fmaf(c[1], sp[n].y, bp[n].y),
-                                   x.z + fmaf(c[2], sp[n].z, bp[n].z), x.w + fmaf(c[3], sp[n].w, bp[n].w)});
-                }
-            }
-        }
+        stage_w(R_F1, pack, SPT_PACK_FC1, 8);           // fc1 weights into the dead K tile
+        if (!(p.abl & 32)) SPT_BY_WAVE(wave, MTS, 1, false, false, 2, ATS, XS, ATT, X, S_W, par, SPT_C_PROJ, 0.f, lane);
         phase_sync();
-        // ---------------- Hid = gelu(LN2(X) . W1^T + b) : 17 x 4 tiles
-        {
-            stage_w(S_W, pack, SPT_PACK_FC2, 8);        // fc2 weights (the proj weights in S_W were read a phase ago)
-            sf16x8 w1[4][2];
-            float4 b1[4], s1[4];
-#pragma unroll
-            for (int n = 0; n < 4; ++n) {
-                load_w(R_F1, n, w1[n]);
-                b1[n] = ::mpl::ld4(par + SPT_C_FC1 + 16 * n + 4 * kq);
-                s1[n] = ::mpl::ld4(par + SPT_NCOL + SPT_C_FC1 + 16 * n + 4 * kq);
-            }
-            const float hs = par[2 * SPT_NCOL + 1];     // half the static scale of the fc2 operand (a power of two)
-            const int lo = (MTS * 4 * wave) / NWAVE, hi = (MTS * 4 * (wave + 1)) / NWAVE;
-            for (int m = lo >> 2; m <= ((hi - 1) >> 2) && !(p.abl & 64); ++m) {
-                sf16x8 ah, al;
-                ln_frag(m, ah, al);
-#pragma unroll
-                for (int n = 0; n < 4; ++n) {
-                    const int u = 4 * m + n;
-                    if (u < lo || u >= hi) continue;
-                    const f32x4 c = mfma3(w1[n], ah, al, f32x4{0.f, 0.f, 0.f, 0.f});
-                    st4(HID + (m * 16 + li) * HS + 16 * n + 4 * kq,
-                        float4{gelu_as_scaled(fmaf(c[0], s1[n].x, b1[n].x), hs), gelu_as_scaled(fmaf(c[1], s1[n].y, b1[n].y), hs),
-                               gelu_as_scaled(fmaf(c[2], s1[n].z, b1[n].z), hs), gelu_as_scaled(fmaf(c[3], s1[n].w, b1[n].w), hs)});
-                }
-            }
-        }
+        // ---------------- Hid = gelu(LN2(X) . W1^T + b) : 17 x 4 tiles; par[449] = half the static scale of the fc2 operand
+        stage_w(S_W, pack, SPT_PACK_FC2, 8);            // fc2 weights (the proj weights in S_W were read a phase ago)
+        if (!(p.abl & 64))
+            SPT_BY_WAVE(wave, MTS, 1, true, true, 4, XS, HS, X, HID, R_F1, par, SPT_C_FC1, par[2 * SPT_NCOL + 1], lane);
         phase_sync();
         // ---------------- X += Hid . W2^T + b : K = 64 (two k steps), 17 x 2 tiles
         {
@@ -441,32 +505,7 @@ __global__ __launch_bounds__(NTHR, 1) void spt3_kernel(const SptParams p) {
                 stage_w(R_Q, bn.qkv_w3, SPT_PACK_QKV, 12);
                 parn = load_par(bn);
             }
-            sf16x8 w2[2][2][2];
-            float4 b2[2], s2[2];
-#pragma unroll
-            for (int n = 0; n < 2; ++n) {
-                load_w(S_W, 2 * n, w2[n][0]);
-                load_w(S_W, 2 * n + 1, w2[n][1]);
-                b2[n] = ::mpl::ld4(par + SPT_C_FC2 + 16 * n + 4 * kq);
-                s2[n] = ::mpl::ld4(par + SPT_NCOL + SPT_C_FC2 + 16 * n + 4 * kq);
-            }
-            const int lo = (MTS * 2 * wave) / NWAVE, hi = (MTS * 2 * (wave + 1)) / NWAVE;
-            for (int m = lo >> 1; m <= ((hi - 1) >> 1) && !(p.abl & 128); ++m) {
-                sf16x8 ah0, al0, ah1, al1;
-                raw_frag(HID + (m * 16 + li) * HS + 8 * kq, ah0, al0);
-                raw_frag(HID + (m * 16 + li) * HS + 32 + 8 * kq, ah1, al1);
-#pragma unroll
-                for (int n = 0; n < 2; ++n) {
-                    const int u = 2 * m + n;
-                    if (u < lo || u >= hi) continue;
-                    f32x4 c = mfma3(w2[n][0], ah0, al0, f32x4{0.f, 0.f, 0.f, 0.f});
-                    c = mfma3(w2[n][1], ah1, al1, c);
-                    float* xd = X + (m * 16 + li) * XS + 16 * n + 4 * kq;
-                    const float4 x = ::mpl::ld4(xd);
-                    st4(xd, float4{x.x + fmaf(c[0], s2[n].x, b2[n].x), x.y + fmaf(c[1], s2[n].y, b2[n].y),
-                                   x.z + fmaf(c[2], s2[n].z, b2[n].z), x.w + fmaf(c[3], s2[n].w, b2[n].w)});
-                }
-            }
+            if (!(p.abl & 128)) SPT_BY_WAVE(wave, MTS, 2, false, false, 2, HS, XS, HID, X, S_W, par, SPT_C_FC2, 0.f, lane);
             if (app + 1 < p.n_apps) store_par(app + 1, parn);
         }
         phase_sync();
