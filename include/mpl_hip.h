@@ -676,6 +676,44 @@ int mpl_triangulate_robust(const float *const *rays, const float *const *centers
                            int batch, int views, int joints, double threshold, double conf_threshold, int min_inliers,
                            float *out_points, float *out_residual, float *out_inliers, void *stream);
 
+/* ---- refinement of 3D points by their reprojection error, csrc/refine.hip.  The triangulations above minimise the distance to the
+ * lines of sight in world units; a detector errs in pixels.  mpl_refine_points minimises, per (sample, joint) and from the point it
+ * is given, E(X) = sum_v w_v rho(|r_v|^2) with r_v = proj_v(X) - px_v in pixels, and reports the reprojection error of the result; with
+ * max_iterations == 0 it is the reprojection error of any 3D estimate.  The reference has no such step.
+ * points (B,J,3), pixels (B,V,J,2), conf (B,V,J) or NULL (every weight 1): the layout of mpl_prepare_inputs; cams_dev (V,16);
+ * dist_dev (V,5) or NULL (the pinhole).  views <= MPL_MAX_VIEWS, joints <= 64, batch * views * joints <= 2^30.
+ * Projection: that of mpl_synthesize_views_ex, x_cam = R (X - t), y = x_cam.xy / z, the lens polynomial above, px = f y_d + c; zero
+ * coefficients give the pinhole projection.  Its Jacobian is analytic: diag(f) (the lens Jacobian of the inverse above)
+ * (d y / d x_cam) R.
+ * Participation: view v takes part in an item when w_v is finite and > 0 and both pixel coordinates are finite.
+ * Cost: huber <= 0 or NaN, the plain mode: rho(s) = s.  huber = h > 0: rho(s) = s if s <= h^2, else 2 h sqrt(s) - h^2.  E is +inf
+ * where a view that takes part has z_cam <= 1e-9 at X.
+ * Iteration: Levenberg-Marquardt on the 3 unknowns.  H = sum w'_v J_v^T J_v, g = sum w'_v J_v^T r_v, w'_v = w_v in the plain mode and
+ * the IRLS weight w_v min(1, h / |r_v|) in the Huber mode; (H + lambda diag H) delta = -g is solved in closed form; lambda starts at
+ * 1e-3.  The trial X + delta is accepted only if its E is strictly lower, then lambda = max(lambda / 10, 1e-15); otherwise lambda *=
+ * 10 and X stays: E never increases.  Every trial counts as one iteration.  After a trial, accepted or not: converged when
+ * max |delta| <= step_tolerance * z_min, z_min the smallest z_cam at (the possibly new) X among the views that take part -- a length
+ * scale that does not know whether the world is in metres or millimetres --; else capped when lambda > 1e12 or after max_iterations
+ * trials.
+ * Outputs per item: out_points (B,J,3) the final point; out_error (B,J) = sqrt(sum w |r|^2 / sum w) at it over the views that take
+ * part, the plain weighted RMS in both modes, so that numbers compare across modes; out_errors (B,V,J) = |r_v| in pixels, NaN for a
+ * view that takes no part; out_iterations (B,J) the trials made; out_status (B,J) bytes:
+ *   0 converged;  1 capped;
+ *   2 passed through: fewer than two views take part, or max_iterations == 0; the point is returned bit for bit and the errors are
+ *     those of the views that take part;
+ *   3 invalid: the given point is not finite, no view takes part, or a view that takes part has the point at z_cam <= 1e-9; point,
+ *     error and errors are NaN.  A statement about the item: no device error, and no other item is touched.
+ * out_errors, out_iterations and out_status may be NULL.
+ * One launch, one thread per item, the views summed in their order, fp64 on the fp32 tensors, every output rounded once, no atomics:
+ * identical bits from run to run and from batching to batching.  Stream-ordered, never synchronises; neither looks at nor sets the
+ * device error word.
+ * MPL_E_INVALID: points, pixels, cams_dev, out_points or out_error NULL, a size that is not positive or beyond the limits above;
+ * MPL_E_UNSUPPORTED: max_iterations outside [0, 1000], a step_tolerance that is negative or not finite -- before any launch. */
+int mpl_refine_points(const float *points, const float *pixels, const float *conf, const double *cams_dev, const double *dist_dev,
+                      int batch, int views, int joints, double huber, int max_iterations, double step_tolerance,
+                      float *out_points, float *out_error, float *out_errors, int *out_iterations, unsigned char *out_status,
+                      void *stream);
+
 /* ---- Procrustes alignment of predicted poses onto their targets, csrc/procrustes.hip: the transform behind PA-MPJPE (Protocol
  * 2), in place of lib/utils/pose_utils.py:61-143 PoseUtils.procrustes (a numpy port of MATLAB's procrustes, one 3x3 SVD per pose
  * on the host, which would force all_preds back to the host).  One launch aligns `batch` poses: target A and prediction B, both

@@ -15,7 +15,8 @@ def __getattr__(name):
     if name == "PoseEvaluator":
         from .evaluate import PoseEvaluator
         return PoseEvaluator
-    if name in ("triangulate_rays", "triangulate_rays_robust", "triangulate_pixels", "epipolar_errors", "consistency_weights"):
+    if name in ("triangulate_rays", "triangulate_rays_robust", "triangulate_pixels", "epipolar_errors", "consistency_weights", "refine_points",
+                "reprojection_errors"):
         from . import geometry
         return getattr(geometry, name)
     if name == "procrustes_align":

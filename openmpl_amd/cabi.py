@@ -130,7 +130,9 @@ EXPORTS = ("mpl_hip_abi_version", "mpl_hip_error_string", "mpl_config_supported"
            "mpl_profile_stop",
            # lens distortion: lib/multiviews/cameras.py:22-46 (project_point_radial) and its inverse, which the reference leaves to pymvg
            # (lib/multiviews/triangulate.py:26-38); the _ex calls are their namesakes for a calibration with k, p
-           "mpl_undistort_points", "mpl_prepare_inputs_ex", "mpl_synthesize_views_ex")
+           "mpl_undistort_points", "mpl_prepare_inputs_ex", "mpl_synthesize_views_ex",
+           # Levenberg-Marquardt on the reprojection error of 3D points, and the error itself; the reference has no such step
+           "mpl_refine_points")
 KINDS = ("spt", "row_stats", "gemm", "attention", "fuse_head", "pack")
 
 _lib = None
@@ -315,6 +317,9 @@ def load():
         lib.mpl_triangulate_robust.restype = C.c_int
         lib.mpl_triangulate_robust.argtypes = [C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_fp), C.c_int, C.c_int, C.c_int, C.c_int,
                                                C.c_double, C.c_double, C.c_int, _fp, _fp, _fp, _fp]
+        lib.mpl_refine_points.restype = C.c_int
+        lib.mpl_refine_points.argtypes = [_fp, _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, _fp, _fp, _fp,
+                                          _fp, _fp, _fp]
         lib.mpl_procrustes_align.restype = C.c_int
         lib.mpl_procrustes_align.argtypes = [_fp, _fp, _fp, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int,
                                              C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, _fp]

@@ -938,6 +938,14 @@ int mpl_triangulate_robust(const float* const* rays, const float* const* centers
                                      out_points, out_residual, out_inliers, (hipStream_t)stream);
 }
 
+int mpl_refine_points(const float* points, const float* pixels, const float* conf, const double* cams_dev, const double* dist_dev,
+                      int batch, int views, int joints, double huber, int max_iterations, double step_tolerance, float* out_points,
+                      float* out_error, float* out_errors, int* out_iterations, unsigned char* out_status, void* stream) {
+    clear_stale_hip_error();
+    return launch_refine_points(points, pixels, conf, cams_dev, dist_dev, batch, views, joints, huber, max_iterations, step_tolerance,
+                                out_points, out_error, out_errors, out_iterations, out_status, (hipStream_t)stream);
+}
+
 int mpl_procrustes_align(const float* pred, const float* target, const float* conf, const int* sel, int n_sel, const float* scale3,
                          const float* offset3, int scaling, int reflection, int batch, int joints, float* aligned, float* d,
                          float* rotation, float* scale, float* translation, void* stream) {

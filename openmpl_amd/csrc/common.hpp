@@ -365,6 +365,11 @@ int launch_triangulate_robust(const float* const* rays, const float* const* cent
                               int V, int J, double threshold, double conf_threshold, int min_inliers, float* points,
                               float* residual, float* inliers, hipStream_t s);
 
+// refine.hip: Levenberg-Marquardt refinement of 3D points on their reprojection error, and the error itself (mpl_refine_points)
+int launch_refine_points(const float* points, const float* pixels, const float* conf, const double* cams_dev, const double* dist_dev,
+                         int B, int V, int J, double huber, int max_iterations, double step_tolerance, float* out_points,
+                         float* out_error, float* out_errors, int* out_iterations, unsigned char* out_status, hipStream_t s);
+
 // synth.hip: model inputs synthesized from 3D poses (mpl_synthesize_views); dist_dev null: the pinhole kernel
 int launch_synthesize_views(const float* poses3d, const double* cams_dev, const double* dist_dev, const mpl_synth_options* opt, const float* conf,
                             const float* rotation_deg, const float* translation, const float* noise, const float* missing_u,

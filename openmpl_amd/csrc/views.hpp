@@ -56,6 +56,24 @@ __device__ __forceinline__ Normalized distort_normalized(double y0, double y1, D
     return Normalized{y0 * g + d.p2 * r2, y1 * g + d.p1 * r2};
 }
 
+// The lens and its analytic 2x2 Jacobian d y_d / d y at one point: the polynomial of distort_normalized and the j00 .. j11 that
+// undistort_normalized forms, for the callers that differentiate the projection (refine.hip).  A function of its own, so that the
+// two above keep their code.
+struct LensJet {
+    double x, y;                             // y_d
+    double j00, j01, j10, j11;
+};
+
+__device__ __forceinline__ LensJet distort_jet(double y0, double y1, Distortion d) {
+    const double r2 = y0 * y0 + y1 * y1;
+    const double g = 1.0 + (d.k1 * r2 + d.k2 * (r2 * r2) + d.k3 * (r2 * r2 * r2)) + (2.0 * d.p1 * y1 + 2.0 * d.p2 * y0);
+    const double gr = d.k1 + 2.0 * d.k2 * r2 + 3.0 * d.k3 * (r2 * r2);                       // dg / dr2
+    const double g0 = 2.0 * (gr * y0 + d.p2), g1 = 2.0 * (gr * y1 + d.p1);                   // dg / dy
+    return LensJet{y0 * g + d.p2 * r2, y1 * g + d.p1 * r2,
+                   g + y0 * g0 + 2.0 * d.p2 * y0, y0 * g1 + 2.0 * d.p2 * y1,
+                   y1 * g0 + 2.0 * d.p1 * y0, g + y1 * g1 + 2.0 * d.p1 * y1};
+}
+
 constexpr int UNDISTORT_MAX_ITER = 20;       // a guard: the coefficient sets of the tests take at most 4 on a centred subject
 constexpr double UNDISTORT_TOL = 1e-14;
 

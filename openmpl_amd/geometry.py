@@ -7,11 +7,14 @@ of V (B,1,3) camera centres -- what prepare_inputs returns and `model(input, cen
 V tensors, each (B,J) or one of the model's own (B,J,3) pose tensors, whose channel 2 is read in place.  Two HIP kernels through the
 C ABI (mpl_triangulate_rays, mpl_epipolar_errors, csrc/geometry.hip) on the current stream; no synchronisation, no CPU path.
 triangulate_rays_robust (mpl_triangulate_robust, a third kernel) puts the view selection of lib/multiviews/triangulate.py:88-112
-and a pair consensus in front of the same least-squares fit.
+and a pair consensus in front of the same least-squares fit.  refine_points / reprojection_errors (mpl_refine_points,
+csrc/refine.hip) work in the detector's unit: Levenberg-Marquardt on the reprojection error of a point in pixels, and that error for
+any 3D estimate.
 """
 from __future__ import annotations
 
-from typing import List, Optional, Sequence, Tuple
+import math
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -127,8 +130,8 @@ def triangulate_rays_robust(rays: Sequence[torch.Tensor], centers: Sequence[torc
 
 def triangulate_pixels(pixels: torch.Tensor, conf: Optional[torch.Tensor], cams: torch.Tensor,
                        image_size: Optional[Tuple[float, float]] = None, distortion: Optional[torch.Tensor] = None,
-                       threshold: Optional[float] = None, conf_threshold: Optional[float] = None
-                       ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+                       threshold: Optional[float] = None, conf_threshold: Optional[float] = None, refine: bool = False,
+                       huber: Optional[float] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """The call shape of the reference's triangulate_poses(camera_params, poses2d, confs) (lib/multiviews/triangulate.py:59-115) for
     a batch: pixels (B,V,J,2) float32 GPU, conf (B,V,J) or None, cams (V,16) float64 (pack_cameras), distortion (V,5) float64
     (pack_distortion) or None -> (points (B,J,3), residual (B,J), inliers (B,V,J)).
@@ -137,11 +140,112 @@ def triangulate_pixels(pixels: torch.Tensor, conf: Optional[torch.Tensor], cams:
     through the undistorted pixels, and a joint whose pixel is not invertible takes no part in that view -- then
     triangulate_rays_robust(rays, centers, poses as the confidences, threshold, conf_threshold), which with both stages off is
     triangulate_rays.  Without normalisation image_size is not looked at; it defaults to (1, 1).  Where the reference hands its
-    coefficients to pymvg's OpenCV model, this inverts the model the projection uses (include/mpl_hip.h)."""
+    coefficients to pymvg's OpenCV model, this inverts the model the projection uses (include/mpl_hip.h).
+
+    refine=True adds a third launch: the returned `points` are those of refine_points(points, pixels, conf * inliers, cams,
+    distortion, huber) -- the linear point moved to the minimum of its reprojection error in pixels over the inlier views (one torch
+    multiply forms the weights; a NaN point stays NaN).  `residual` and `inliers` stay those of the linear stage.  `huber` (pixels)
+    without `refine` raises.  With the default the call makes the two launches it always made and returns the same bits."""
     from .inputs import prepare_inputs
+    if huber is not None and not refine:
+        raise RuntimeError("huber is an option of the refinement: it needs refine=True")
     poses, rays, centers = prepare_inputs(pixels, conf, cams, (1.0, 1.0) if image_size is None else image_size, False, False,
                                           distortion=distortion)
-    return triangulate_rays_robust(rays, centers, poses, threshold=threshold, conf_threshold=conf_threshold)
+    points, residual, inliers = triangulate_rays_robust(rays, centers, poses, threshold=threshold, conf_threshold=conf_threshold)
+    if refine:
+        weight = inliers if conf is None else conf.reshape(inliers.shape).to(torch.float32) * inliers
+        points = refine_points(points, pixels, weight, cams, distortion=distortion, huber=huber).points
+    return points, residual, inliers
+
+
+class Refined(NamedTuple):
+    """what refine_points returns"""
+    points: torch.Tensor          # (B,J,3) float32
+    error: torch.Tensor           # (B,J) float32: the weighted root-mean-square reprojection error, pixels
+    errors: torch.Tensor          # (B,V,J) float32: |r_v| in pixels, NaN for a view that takes no part
+    iterations: torch.Tensor      # (B,J) int32: trial steps made
+    status: torch.Tensor          # (B,J) uint8: 0 converged, 1 capped, 2 passed through, 3 invalid
+
+
+def _observations(points, pixels, conf, cams, distortion):
+    """The argument checks of refine_points in the order of _lines: shapes first, then dtypes, then devices, each complaint naming
+    its argument and raised before any device is touched; cams and distortion as prepare_inputs checks them."""
+    from .inputs import check_distortion
+    for what, t in (("points", points), ("pixels", pixels)) + ((("conf", conf),) if conf is not None else ()):
+        if not isinstance(t, torch.Tensor):
+            raise RuntimeError("%s must be a tensor" % what)
+    if pixels.ndim != 4 or pixels.shape[3] != 2 or min(pixels.shape[:3]) < 1:
+        raise RuntimeError("pixels: expected shape (B,V,J,2), got %s" % (tuple(pixels.shape),))
+    B, V, J, _ = pixels.shape
+    groups = [("points", points, (B, J, 3)), ("pixels", pixels, (B, V, J, 2))] + ([("conf", conf, (B, V, J))] if conf is not None else [])
+    for what, t, shape in groups:
+        if tuple(t.shape) != shape:
+            raise RuntimeError("%s: expected shape %s, got %s" % (what, shape, tuple(t.shape)))
+    for what, t, _ in groups:
+        if t.dtype != torch.float32:
+            raise RuntimeError("float32 tensors required (%s is %s)" % (what, t.dtype))
+    dev = pixels.device
+    for what, t, _ in groups:
+        if t.device.type != "cuda":
+            raise RuntimeError("the geometry kernels have no CPU path: %s must live on a GPU" % what)
+        if t.device != dev:
+            raise RuntimeError("%s is on %s, pixels on %s" % (what, t.device, dev))
+    if not isinstance(cams, torch.Tensor) or tuple(cams.shape) != (V, 16) or cams.dtype != torch.float64 or cams.device != dev:
+        raise RuntimeError("cams must be float64 (V,16) on the same device (see pack_cameras)")
+    distortion = check_distortion(distortion, V, dev)
+    if V > cabi.MPL_MAX_VIEWS or J > 64 or B * V * J > 1 << 30:
+        raise NotImplementedError("at most %d views, 64 joints and 2^30 observations (got %d, %d, %d)" % (cabi.MPL_MAX_VIEWS, V, J, B * V * J))
+    return [t.contiguous() for _, t, _ in groups] + [None] * (conf is None), cams.contiguous(), distortion, B, V, J
+
+
+def _refine(points, pixels, conf, cams, distortion, huber, max_iterations, step_tolerance):
+    (points, pixels, conf), cams, distortion, B, V, J = _observations(points, pixels, conf, cams, distortion)
+    dev = pixels.device
+    out = Refined(torch.empty((B, J, 3), dtype=torch.float32, device=dev), torch.empty((B, J), dtype=torch.float32, device=dev),
+                  torch.empty((B, V, J), dtype=torch.float32, device=dev), torch.empty((B, J), dtype=torch.int32, device=dev),
+                  torch.empty((B, J), dtype=torch.uint8, device=dev))
+    cabi.launch("refine_points", dev, points.data_ptr(), pixels.data_ptr(), ptr(conf), cams.data_ptr(), ptr(distortion), B, V, J, huber,
+                max_iterations, step_tolerance, *(t.data_ptr() for t in out))
+    return out
+
+
+def refine_points(points: torch.Tensor, pixels: torch.Tensor, conf: Optional[torch.Tensor], cams: torch.Tensor,
+                  distortion: Optional[torch.Tensor] = None, huber: Optional[float] = None, max_iterations: int = 20,
+                  step_tolerance: float = 1e-8) -> Refined:
+    """points (B,J,3) moved to the minimum of their reprojection error: E(X) = sum_v w_v rho(|proj_v(X) - pixels_v|^2) in pixels,
+    by Levenberg-Marquardt from the given point.  pixels (B,V,J,2), conf (B,V,J) or None (the weights w), cams (V,16) float64,
+    distortion (V,5) float64 or None: the arguments of triangulate_pixels, and the projection of project_points(distortion=).
+    -> Refined(points, error, errors, iterations, status).
+
+    A view takes part when its weight is finite and > 0 and its pixel is finite.  huber=None: rho(s) = s, least squares.
+    huber=h (pixels): rho(s) = s up to h^2, 2 h sqrt(s) - h^2 beyond -- a detection far off pulls with a bounded force; the soft
+    counterpart of the pair consensus of triangulate_rays_robust, in the detector's unit.  A trial step is accepted only if it
+    lowers E, so E never rises; every trial counts in `iterations`, at most `max_iterations` (0 .. 1000).  Converged (status 0) when
+    the step is <= step_tolerance times the depth of the nearest camera, else capped (1).  Passed through (2): fewer than two views
+    take part or max_iterations == 0; the point is returned bit for bit.  Invalid (3): the point is not finite, no view takes part,
+    or the point lies behind a camera that takes part; point, error and errors are NaN.  error (B,J) is the weighted
+    root-mean-square of |r_v| in both modes, errors (B,V,J) the |r_v|, NaN where a view takes no part.  One launch, no
+    synchronisation, identical bits from run to run and from batching to batching."""
+    h = 0.0                                              # the C ABI's "plain"
+    if huber is not None:
+        h = float(huber)
+        if not (h > 0.0 and math.isfinite(h)):
+            raise RuntimeError("huber must be a positive finite number of pixels (got %r)" % (huber,))
+    if int(max_iterations) != max_iterations or not 0 <= max_iterations <= 1000:
+        raise RuntimeError("max_iterations must be an integer in [0, 1000] (got %r)" % (max_iterations,))
+    tol = float(step_tolerance)
+    if not (tol >= 0.0 and math.isfinite(tol)):
+        raise RuntimeError("step_tolerance must be a finite number >= 0 (got %r)" % (step_tolerance,))
+    return _refine(points, pixels, conf, cams, distortion, h, int(max_iterations), tol)
+
+
+def reprojection_errors(points: torch.Tensor, pixels: torch.Tensor, conf: Optional[torch.Tensor], cams: torch.Tensor,
+                        distortion: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The score of a 3D estimate in image units, which needs no ground truth: (errors (B,V,J), error (B,J)) of refine_points at
+    the points as they are (the same launch with max_iterations=0).  points (B,J,3): triangulated points, rpsm poses, or the model's
+    predictions after de-normalisation."""
+    r = _refine(points, pixels, conf, cams, distortion, 0.0, 0, 0.0)
+    return r.errors, r.error
 
 
 def _epipolar(rays, centers, conf, weight, threshold):
