@@ -714,6 +714,43 @@ int mpl_refine_points(const float *points, const float *pixels, const float *con
                       float *out_points, float *out_error, float *out_errors, int *out_iterations, unsigned char *out_status,
                       void *stream);
 
+/* ---- refinement of the camera poses by the same error, csrc/refine_cameras.hip: the transpose of mpl_refine_points.  The points are
+ * given and the cameras move: per view v, from the pose it is given, E_v(R, t) = sum_{b,j} w_bvj rho(|r_bvj|^2) with
+ * r = proj_v(X_bj) - px_bvj in pixels is minimised over the 6 unknowns of the pose.  Arguments, layouts, limits, projection, lens,
+ * weights and rho are those of mpl_refine_points; the intrinsics and the lens row are not unknowns (the intrinsics are copied to
+ * the output).  The reference has no such step (its PoseUtils.estimate_camera is a weak-perspective fit).
+ * Participation: observation (b, j) of view v takes part when its weight is finite and > 0, its pixel is finite and the three
+ * coordinates of X_bj are finite -- NaN joints of a triangulation drop out.  out_used[v] counts them.
+ * Parametrisation: a trial pose is R' = exp([w]x) R, t' = t + dt, delta = (w, dt); exp([w]x) = I + a K + b K^2 with K = [w]x,
+ * a = sin(th) / th, b = (1 - cos(th)) / th^2 (their series below th^2 = 1e-8), in fp64.  With x_cam = R (X - t) and M = d px / d x_cam
+ * the 2x6 Jacobian is M [ -[x_cam]x | -R ].
+ * Iteration: the loop of mpl_refine_points on 6 unknowns.  H = sum w' J^T J, g = sum w' J^T r with the IRLS weights;
+ * (H + lambda diag H) delta = -g by an unpivoted Cholesky factorisation (a pivot that is <= 0 or not finite gives a NaN step, which
+ * no trial survives); lambda starts at 1e-3; a trial that lowers E strictly and leaves every participating point at z_cam > 1e-9 is
+ * accepted, then lambda = max(lambda / 10, 1e-15); otherwise lambda *= 10 and the pose stays: E never increases.  After a trial,
+ * accepted or not: converged when max |w| <= step_tolerance and max |dt| <= step_tolerance * z_min, z_min the smallest depth of a
+ * participating point at the accepted pose; else capped when lambda > 1e12 or after max_iterations trials.
+ * Outputs per view: out_cams (V,16) the record with the final pose; out_error (V) = sqrt(sum w |r|^2 / sum w) there, the plain
+ * weighted RMS in pixels in both modes; out_cost0, out_cost (V) = E at the given and at the final pose, in the mode of the call, so
+ * out_cost <= out_cost0; out_used, out_iterations (V) ints; out_status (V) bytes:
+ *   0 converged;  1 capped;
+ *   2 passed through: bit v of fixed_mask is set, max_iterations == 0, or fewer than 3 observations take part; the record is
+ *     returned bit for bit, error and costs are computed, out_cost == out_cost0;
+ *   3 invalid: no observation takes part, the given record is not finite, or a participating point is not in front of the given
+ *     camera; the record is returned as given (a NaN row would poison every later call), error and costs are NaN.  A statement
+ *     about the view: no device error, and no other view is touched.
+ * Bits of fixed_mask at or above `views` are ignored.  conf, dist_dev, out_cost0, out_cost, out_used, out_iterations and
+ * out_status may be NULL.  out_cams may be cams_dev: a workgroup reads its row before it writes it and touches no other row.
+ * One launch, one workgroup per view; the sums over the observations are fp64, reduced down the waves and across them in a fixed
+ * order, without atomics: identical bits from run to run.  Stream-ordered, never synchronises; neither looks at nor sets the device
+ * error word.  The trial count is bounded by max_iterations whatever the data.
+ * MPL_E_INVALID: points, pixels, cams_dev, out_cams or out_error NULL, a size that is not positive or beyond the limits;
+ * MPL_E_UNSUPPORTED: max_iterations outside [0, 1000], a step_tolerance that is negative or not finite -- before any launch. */
+int mpl_refine_cameras(const float *points, const float *pixels, const float *conf, const double *cams_dev, const double *dist_dev,
+                       int batch, int views, int joints, double huber, int max_iterations, double step_tolerance, unsigned fixed_mask,
+                       double *out_cams, double *out_error, double *out_cost0, double *out_cost, int *out_used, int *out_iterations,
+                       unsigned char *out_status, void *stream);
+
 /* ---- Procrustes alignment of predicted poses onto their targets, csrc/procrustes.hip: the transform behind PA-MPJPE (Protocol
  * 2), in place of lib/utils/pose_utils.py:61-143 PoseUtils.procrustes (a numpy port of MATLAB's procrustes, one 3x3 SVD per pose
  * on the host, which would force all_preds back to the host).  One launch aligns `batch` poses: target A and prediction B, both

@@ -132,7 +132,9 @@ EXPORTS = ("mpl_hip_abi_version", "mpl_hip_error_string", "mpl_config_supported"
            # (lib/multiviews/triangulate.py:26-38); the _ex calls are their namesakes for a calibration with k, p
            "mpl_undistort_points", "mpl_prepare_inputs_ex", "mpl_synthesize_views_ex",
            # Levenberg-Marquardt on the reprojection error of 3D points, and the error itself; the reference has no such step
-           "mpl_refine_points")
+           "mpl_refine_points",
+           # the transpose: Levenberg-Marquardt on the 6 pose unknowns of every camera, the points given; no counterpart either
+           "mpl_refine_cameras")
 KINDS = ("spt", "row_stats", "gemm", "attention", "fuse_head", "pack")
 
 _lib = None
@@ -320,6 +322,9 @@ def load():
         lib.mpl_refine_points.restype = C.c_int
         lib.mpl_refine_points.argtypes = [_fp, _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, _fp, _fp, _fp,
                                           _fp, _fp, _fp]
+        lib.mpl_refine_cameras.restype = C.c_int
+        lib.mpl_refine_cameras.argtypes = [_fp, _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, C.c_uint,
+                                           _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp]
         lib.mpl_procrustes_align.restype = C.c_int
         lib.mpl_procrustes_align.argtypes = [_fp, _fp, _fp, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int,
                                              C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, _fp]

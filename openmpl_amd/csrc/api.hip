@@ -946,6 +946,16 @@ int mpl_refine_points(const float* points, const float* pixels, const float* con
                                 out_points, out_error, out_errors, out_iterations, out_status, (hipStream_t)stream);
 }
 
+int mpl_refine_cameras(const float* points, const float* pixels, const float* conf, const double* cams_dev, const double* dist_dev,
+                       int batch, int views, int joints, double huber, int max_iterations, double step_tolerance, unsigned fixed_mask,
+                       double* out_cams, double* out_error, double* out_cost0, double* out_cost, int* out_used, int* out_iterations,
+                       unsigned char* out_status, void* stream) {
+    clear_stale_hip_error();
+    return launch_refine_cameras(points, pixels, conf, cams_dev, dist_dev, batch, views, joints, huber, max_iterations, step_tolerance,
+                                 fixed_mask, out_cams, out_error, out_cost0, out_cost, out_used, out_iterations, out_status,
+                                 (hipStream_t)stream);
+}
+
 int mpl_procrustes_align(const float* pred, const float* target, const float* conf, const int* sel, int n_sel, const float* scale3,
                          const float* offset3, int scaling, int reflection, int batch, int joints, float* aligned, float* d,
                          float* rotation, float* scale, float* translation, void* stream) {

@@ -370,6 +370,12 @@ int launch_refine_points(const float* points, const float* pixels, const float* 
                          int B, int V, int J, double huber, int max_iterations, double step_tolerance, float* out_points,
                          float* out_error, float* out_errors, int* out_iterations, unsigned char* out_status, hipStream_t s);
 
+// refine_cameras.hip: Levenberg-Marquardt refinement of the camera poses on the same error, one workgroup per view (mpl_refine_cameras)
+int launch_refine_cameras(const float* points, const float* pixels, const float* conf, const double* cams_dev, const double* dist_dev,
+                          int B, int V, int J, double huber, int max_iterations, double step_tolerance, unsigned fixed_mask,
+                          double* out_cams, double* out_error, double* out_cost0, double* out_cost, int* out_used, int* out_iterations,
+                          unsigned char* out_status, hipStream_t s);
+
 // synth.hip: model inputs synthesized from 3D poses (mpl_synthesize_views); dist_dev null: the pinhole kernel
 int launch_synthesize_views(const float* poses3d, const double* cams_dev, const double* dist_dev, const mpl_synth_options* opt, const float* conf,
                             const float* rotation_deg, const float* translation, const float* noise, const float* missing_u,
