@@ -133,6 +133,11 @@ __device__ __forceinline__ float gelu_as_scaled(float x, float hs) {
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ void st4(float* p, const float4& v) { *reinterpret_cast<float4*>(p) = v; }
 
+// ---- what counts in the fp64 pose utilities: the largest finite double, and the weight (a confidence) of an observation, a view or
+// a joint that takes part -- w <= 0, NaN or inf does not
+constexpr double FINITE_MAX = 1.79769313486231570e308;
+__device__ __forceinline__ bool takes_part(double w) { return w > 0.0 && w <= FINITE_MAX; }
+
 // ---- optional per-launch event bracketing (mpl_profile_start/stop) ----------------------------
 struct ProfScope {
     ProfScope(int kind, hipStream_t s);

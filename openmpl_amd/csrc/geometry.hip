@@ -31,10 +31,6 @@ struct GeoViews {
 };
 
 constexpr double DET_MIN = 1e-10;         // det(A / sum w) below this: degenerate (two views: sin^2(angle) / 4)
-constexpr double W_MAX = 1.79769313486231570e308;
-
-// w <= 0, NaN or inf: the view does not take part
-__device__ inline bool takes_part(double w) { return w > 0.0 && w <= W_MAX; }
 
 // The lines of one item as the kernels hold them: in the V tensors themselves, or staged in LDS (item index fastest).
 struct GlobalLines {

@@ -38,9 +38,7 @@ struct ProcArgs {
 };
 
 __device__ __forceinline__ bool proc_takes_part(const ProcArgs& p, size_t b, int j) {
-    if (!p.conf) return true;
-    const double c = (double)p.conf[b * p.J + j];
-    return c > 0.0 && c <= 1.79769313486231570e308;        // conf <= 0, NaN or inf: the joint does not take part
+    return !p.conf || takes_part((double)p.conf[b * p.J + j]);
 }
 
 // one Hestenes rotation: columns a and b of M (and of V) are turned so that a . b = 0
@@ -112,7 +110,7 @@ __global__ __launch_bounds__(PROC_POSES) void procrustes_align_kernel(const Proc
         m20 += a2 * b0; m21 += a2 * b1; m22 += a2 * b2;
     }
     // degenerate input (a statement about the pose, not a device error): fewer than 3 joints, a zero or non-finite spread
-    bool bad = cnt < 3 || !(ssX > 0.0 && ssX <= 1.79769313486231570e308) || !(ssY > 0.0 && ssY <= 1.79769313486231570e308);
+    bool bad = cnt < 3 || !(ssX > 0.0 && ssX <= FINITE_MAX) || !(ssY > 0.0 && ssY <= FINITE_MAX);
     const double a_norm = sqrt(ssX), b_norm = sqrt(ssY);
     const double inv_ab = 1.0 / (a_norm * b_norm);
     m00 *= inv_ab; m01 *= inv_ab; m02 *= inv_ab;

@@ -11,15 +11,13 @@
 // of the views: identical bits from run to run and from batching to batching.  Workgroups of one wave: at the headline size
 // (1024 x 17 items) that is about one wave per compute unit, and the kernel is a chain of dependent fp64 operations per lane.
 #include "common.hpp"
-#include "views.hpp"
+#include "reprojection.hpp"
 
 namespace mpl {
 
 namespace {
 
 constexpr int REFINE_THREADS = 64;
-constexpr double REFINE_LAMBDA0 = 1e-3, REFINE_LAMBDA_MIN = 1e-15, REFINE_LAMBDA_MAX = 1e12;
-constexpr double REFINE_W_MAX = 1.79769313486231570e308;
 
 struct RefineParams {
     const float* points;      // (B,J,3)
@@ -140,15 +138,15 @@ __global__ __launch_bounds__(REFINE_THREADS) void refine_points_kernel(const Ref
     for (int v = 0; v < V; ++v) {
         const double w = it.weight(v);
         const float* q = p.px + it.at(v) * 2u;
-        const bool in = w > 0.0 && w <= REFINE_W_MAX && isfinite(q[0]) && isfinite(q[1]);
+        const bool in = takes_part(w) && isfinite(q[0]) && isfinite(q[1]);
         mask |= (unsigned)in << v;
         n += in;
     }
     // One call site of the evaluation: the first pass of the loop evaluates the given point, every later one a trial step.
     RefineEval cur;
     bool valid = isfinite(x0) && isfinite(x1) && isfinite(x2) && n > 0, first = true;
-    int status = 3, trials = 0;
-    double lambda = REFINE_LAMBDA0, Xt[3] = {X[0], X[1], X[2]}, delta[3] = {0, 0, 0};
+    int status = LM_INVALID, trials = 0;
+    double lambda = LM_LAMBDA0, Xt[3] = {X[0], X[1], X[2]}, delta[3] = {0, 0, 0};
     while (valid) {
         const RefineEval tr = refine_eval<LENS>(it, mask, Xt, p.huber);
         if (first) {
@@ -156,24 +154,24 @@ __global__ __launch_bounds__(REFINE_THREADS) void refine_points_kernel(const Ref
             valid = !tr.behind;
             if (!valid) break;
             cur = tr;
-            status = 2;
+            status = LM_PASSED_THROUGH;
             if (n < 2 || p.max_it == 0) break;
-            status = 1;
+            status = LM_CAPPED;
         } else {
             ++trials;
             if (!tr.behind && tr.E < cur.E) {            // strictly lower; a cost that is not a number is never accepted
                 cur = tr;
 #pragma unroll
                 for (int k = 0; k < 3; ++k) X[k] = Xt[k];
-                lambda = fmax(lambda / 10.0, REFINE_LAMBDA_MIN);
+                lambda = fmax(lambda / 10.0, LM_LAMBDA_MIN);
             } else {
                 lambda *= 10.0;
             }
             if (fmax(fabs(delta[0]), fmax(fabs(delta[1]), fabs(delta[2]))) <= p.tol * cur.zmin) {
-                status = 0;
+                status = LM_CONVERGED;
                 break;
             }
-            if (lambda > REFINE_LAMBDA_MAX || trials >= p.max_it) break;
+            if (lambda > LM_LAMBDA_MAX || trials >= p.max_it) break;
         }
         refine_step(cur, lambda, delta);
 #pragma unroll
@@ -208,10 +206,7 @@ __global__ __launch_bounds__(REFINE_THREADS) void refine_points_kernel(const Ref
 int launch_refine_points(const float* points, const float* pixels, const float* conf, const double* cams_dev, const double* dist_dev,
                          int B, int V, int J, double huber, int max_iterations, double step_tolerance, float* out_points,
                          float* out_error, float* out_errors, int* out_iterations, unsigned char* out_status, hipStream_t s) {
-    if (!points || !pixels || !cams_dev || !out_points || !out_error || B <= 0 || V <= 0 || J <= 0) return MPL_E_INVALID;
-    if (V > MPL_MAX_VIEWS || J > 64 || (long long)B * V * J > (1ll << 30)) return MPL_E_INVALID;
-    if (max_iterations < 0 || max_iterations > 1000 || !(step_tolerance >= 0.0) || !(step_tolerance <= REFINE_W_MAX))
-        return MPL_E_UNSUPPORTED;
+    if (const int e = refine_args_check(points, pixels, cams_dev, out_points, out_error, B, V, J, max_iterations, step_tolerance)) return e;
     RefineParams p;
     p.points = points; p.px = pixels; p.conf = conf; p.cams = cams_dev; p.dist = dist_dev;
     p.out_points = out_points; p.out_error = out_error; p.out_errors = out_errors; p.out_iterations = out_iterations;

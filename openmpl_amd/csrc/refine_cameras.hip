@@ -12,7 +12,7 @@
 // factorises, forms the next trial pose and publishes it and a `done` word through LDS.  Every thread reaches every barrier: the
 // loop ends only on that word, read by all threads after a barrier, and the trial count is bounded by max_iterations.
 #include "common.hpp"
-#include "views.hpp"
+#include "reprojection.hpp"
 
 namespace mpl {
 
@@ -22,8 +22,6 @@ namespace {
 // factorisation unrolled into registers (234 in all with a lens, no scratch, no spills); at B J = 17408 that is 34 observations per thread and
 // evaluation
 constexpr int RCAM_THREADS = 512, RCAM_WAVES = RCAM_THREADS / 64;
-constexpr double RCAM_LAMBDA0 = 1e-3, RCAM_LAMBDA_MIN = 1e-15, RCAM_LAMBDA_MAX = 1e12;
-constexpr double RCAM_W_MAX = 1.79769313486231570e308;
 constexpr double RCAM_SMALL_ANGLE2 = 1e-8;
 
 // What one evaluation at a pose leaves behind, as slots of an LDS row: the cost E in the mode of the call, the plain sum S = sum w
@@ -65,7 +63,7 @@ __device__ __forceinline__ void rcam_accumulate(const RefineCamerasParams& p, un
         const float* x = p.points + (size_t)i * 3;
         const float x0 = x[0], x1 = x[1], x2 = x[2];
         // takes part: a finite weight > 0, a finite pixel, a finite point
-        if (!(w > 0.0 && w <= RCAM_W_MAX && isfinite(q0) && isfinite(q1) && isfinite(x0) && isfinite(x1) && isfinite(x2))) continue;
+        if (!(takes_part(w) && isfinite(q0) && isfinite(q1) && isfinite(x0) && isfinite(x1) && isfinite(x2))) continue;
         ++used;
         double xc, yc, zc;
         camera_coords(c, (double)x0, (double)x1, (double)x2, xc, yc, zc);
@@ -125,7 +123,7 @@ __device__ __forceinline__ void rcam_step(const double* e, double lambda, double
         double dj = A[j][j];
 #pragma unroll
         for (int k = 0; k < j; ++k) dj -= L[j][k] * L[j][k];
-        ok = ok && dj > 0.0 && dj <= RCAM_W_MAX;
+        ok = ok && dj > 0.0 && dj <= FINITE_MAX;
         L[j][j] = sqrt(dj);
 #pragma unroll
         for (int i = j + 1; i < 6; ++i) {
@@ -203,7 +201,7 @@ __global__ __launch_bounds__(RCAM_THREADS) void refine_cameras_kernel(const Refi
 
     const bool fits = !(p.fixed_mask >> v & 1u) && p.max_it != 0;           // otherwise passed through, and scored only
     bool first = true;
-    int status = 3, trials = 0, used_out = 0;            // thread 0's
+    int status = LM_INVALID, trials = 0, used_out = 0;   // thread 0's
 
     // One call site of the evaluation: the first pass evaluates the given pose, every later one a trial pose
     for (;;) {
@@ -253,18 +251,18 @@ __global__ __launch_bounds__(RCAM_THREADS) void refine_cameras_kernel(const Refi
                 used_out = (int)sh_tr[RCAM_USED];
                 bool valid = used_out > 0 && sh_tr[RCAM_BEHIND] == 0.0;
 #pragma unroll
-                for (int k = 0; k < 16; ++k) valid = valid && fabs(c[k]) <= RCAM_W_MAX;
+                for (int k = 0; k < 16; ++k) valid = valid && fabs(c[k]) <= FINITE_MAX;
 #pragma unroll
                 for (int k = 0; k < 12; ++k) sh_pose[k] = c[4 + k];
                 if (!valid) {
-                    done = true;                                              // status 3
+                    done = true;                                              // LM_INVALID
                 } else {
                     accept = true;
                     sh_E0 = sh_tr[RCAM_E];
-                    sh_lambda = RCAM_LAMBDA0;
-                    status = 2;
+                    sh_lambda = LM_LAMBDA0;
+                    status = LM_PASSED_THROUGH;
                     if (!fits || used_out < 3) done = true;
-                    else status = 1;
+                    else status = LM_CAPPED;
                 }
             } else {
                 ++trials;
@@ -272,7 +270,7 @@ __global__ __launch_bounds__(RCAM_THREADS) void refine_cameras_kernel(const Refi
                 accept = sh_tr[RCAM_BEHIND] == 0.0 && sh_tr[RCAM_E] < sh_cur[RCAM_E];
                 if (accept) {
                     for (int k = 0; k < 12; ++k) sh_pose[k] = sh_cam[4 + k];
-                    sh_lambda = fmax(sh_lambda / 10.0, RCAM_LAMBDA_MIN);
+                    sh_lambda = fmax(sh_lambda / 10.0, LM_LAMBDA_MIN);
                 } else {
                     sh_lambda = sh_lambda * 10.0;
                 }
@@ -285,9 +283,9 @@ __global__ __launch_bounds__(RCAM_THREADS) void refine_cameras_kernel(const Refi
                 bool small = true;                                            // a step that is not a number is below nothing
                 for (int k = 0; k < 6; ++k) small = small && fabs(sh_delta[k]) <= (k < 3 ? p.tol : tt);
                 if (small) {
-                    status = 0;
+                    status = LM_CONVERGED;
                     done = true;
-                } else if (sh_lambda > RCAM_LAMBDA_MAX || trials >= p.max_it) {
+                } else if (sh_lambda > LM_LAMBDA_MAX || trials >= p.max_it) {
                     done = true;
                 }
             }
@@ -309,7 +307,7 @@ __global__ __launch_bounds__(RCAM_THREADS) void refine_cameras_kernel(const Refi
         // Intrinsics as given; the pose the last accepted one, which is the given row's bits where nothing was accepted -- passed
         // through or invalid: a row that is not a number would poison every later call, so it is handed back, not replaced
         const double nan = __builtin_nan("");
-        const bool valid = status != 3;
+        const bool valid = status != LM_INVALID;
         double* row = p.out_cams + (size_t)v * 16;
 #pragma unroll
         for (int k = 0; k < 4; ++k) row[k] = sh_cam[k];
@@ -328,10 +326,7 @@ int launch_refine_cameras(const float* points, const float* pixels, const float*
                           int B, int V, int J, double huber, int max_iterations, double step_tolerance, unsigned fixed_mask,
                           double* out_cams, double* out_error, double* out_cost0, double* out_cost, int* out_used, int* out_iterations,
                           unsigned char* out_status, hipStream_t s) {
-    if (!points || !pixels || !cams_dev || !out_cams || !out_error || B <= 0 || V <= 0 || J <= 0) return MPL_E_INVALID;
-    if (V > MPL_MAX_VIEWS || J > 64 || (long long)B * V * J > (1ll << 30)) return MPL_E_INVALID;
-    if (max_iterations < 0 || max_iterations > 1000 || !(step_tolerance >= 0.0) || !(step_tolerance <= RCAM_W_MAX))
-        return MPL_E_UNSUPPORTED;
+    if (const int e = refine_args_check(points, pixels, cams_dev, out_cams, out_error, B, V, J, max_iterations, step_tolerance)) return e;
     RefineCamerasParams p;
     p.points = points; p.px = pixels; p.conf = conf; p.cams = cams_dev; p.dist = dist_dev;
     p.out_cams = out_cams; p.out_error = out_error; p.out_cost0 = out_cost0; p.out_cost = out_cost; p.out_used = out_used;

@@ -85,11 +85,11 @@ __device__ __forceinline__ bool rpsm_project(const RpsmParams& p, int b, int v, 
     camera_coords(cam.c, X, Y, Z, xc, yc, zc);
     if (zc <= CAMERA_Z_MIN) return false;
     const Normalized yd = distort_normalized(xc / zc, yc / zc, distortion_of(p.dist, v));   // a null table: the pinhole, bit for bit
-    const double px = cam.fx() * yd.x + cam.cx(), py = cam.fy() * yd.y + cam.cy();
+    const Pixel px = pixel_of(cam, yd.x, yd.y);
     const size_t bv = ((size_t)b * p.V + v) * 2;
     const double k = p.img_w / (200.0 * (double)p.scale[bv]);
-    ux = ((px - (double)p.center[bv]) * k + p.img_w * 0.5) * (double)p.W / p.img_w;
-    uy = ((py - (double)p.center[bv + 1]) * k + p.img_h * 0.5) * (double)p.H / p.img_h;
+    ux = ((px.x - (double)p.center[bv]) * k + p.img_w * 0.5) * (double)p.W / p.img_w;
+    uy = ((px.y - (double)p.center[bv + 1]) * k + p.img_h * 0.5) * (double)p.H / p.img_h;
     return true;
 }
 

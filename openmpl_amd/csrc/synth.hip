@@ -92,9 +92,10 @@ __global__ __launch_bounds__(256) void synthesize_views_kernel(const P p) {
     if (front) {
         if constexpr (P::DIST) {       // px = fx (y0 g + p2 r2) + cx, the form of rpsm_project
             const Normalized yd = distort_normalized(xc / zc, yc / zc, distortion_of(p.dist, v));
-            x = cam.fx() * yd.x + cam.cx();
-            y = cam.fy() * yd.y + cam.cy();
-        } else {
+            const Pixel px = pixel_of(cam, yd.x, yd.y);
+            x = px.x;
+            y = px.y;
+        } else {                       // its own expression: fx * xc / zc rounds otherwise than fx * (xc / zc), and the pinhole goldens pin it
             x = cam.fx() * xc / zc + cam.cx();
             y = cam.fy() * yc / zc + cam.cy();
         }

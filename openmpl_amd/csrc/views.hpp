@@ -48,17 +48,10 @@ struct Normalized {                          // a point in normalised camera coo
     double x, y;
 };
 
-// a pinhole point -> the same after the lens: y (1 + radial + tangential) + (p2, p1) r2.  Contraction is the compiler's default, as
-// it was while rpsm_project held this expression; arguments and result go by value, which is what keeps rpsm's roundings in place
-__device__ __forceinline__ Normalized distort_normalized(double y0, double y1, Distortion d) {
-    const double r2 = y0 * y0 + y1 * y1;
-    const double g = 1.0 + (d.k1 * r2 + d.k2 * (r2 * r2) + d.k3 * (r2 * r2 * r2)) + (2.0 * d.p1 * y1 + 2.0 * d.p2 * y0);
-    return Normalized{y0 * g + d.p2 * r2, y1 * g + d.p1 * r2};
-}
-
-// The lens and its analytic 2x2 Jacobian d y_d / d y at one point: the polynomial of distort_normalized and the j00 .. j11 that
-// undistort_normalized forms, for the callers that differentiate the projection (refine.hip).  A function of its own, so that the
-// two above keep their code.
+// The lens at one point with its analytic 2x2 Jacobian d y_d / d y: a pinhole point -> the same after the lens,
+// y (1 + radial + tangential) + (p2, p1) r2.  The one statement of the polynomial; a caller that reads only part of the jet pays for
+// that part.  Contraction is the compiler's default, as it was while rpsm_project held this expression; arguments and result go by
+// value, which is what keeps rpsm's roundings in place
 struct LensJet {
     double x, y;                             // y_d
     double j00, j01, j10, j11;
@@ -74,6 +67,20 @@ __device__ __forceinline__ LensJet distort_jet(double y0, double y1, Distortion 
                    y1 * g0 + 2.0 * d.p1 * y0, g + y1 * g1 + 2.0 * d.p1 * y1};
 }
 
+__device__ __forceinline__ Normalized distort_normalized(double y0, double y1, Distortion d) {
+    const LensJet jet = distort_jet(y0, y1, d);
+    return Normalized{jet.x, jet.y};
+}
+
+// a point after the lens -> its pixel, f y_d + c
+struct Pixel {
+    double x, y;
+};
+
+__device__ __forceinline__ Pixel pixel_of(const Camera& cam, double yd0, double yd1) {
+    return Pixel{cam.fx() * yd0 + cam.cx(), cam.fy() * yd1 + cam.cy()};
+}
+
 constexpr int UNDISTORT_MAX_ITER = 20;       // a guard: the coefficient sets of the tests take at most 4 on a centred subject
 constexpr double UNDISTORT_TOL = 1e-14;
 
@@ -84,16 +91,11 @@ __device__ __forceinline__ bool undistort_normalized(double yd0, double yd1, Dis
     y0 = yd0;
     y1 = yd1;
     for (int it = 0; it < UNDISTORT_MAX_ITER; ++it) {
-        const double r2 = y0 * y0 + y1 * y1;
-        const double g = 1.0 + (d.k1 * r2 + d.k2 * (r2 * r2) + d.k3 * (r2 * r2 * r2)) + (2.0 * d.p1 * y1 + 2.0 * d.p2 * y0);
-        const double gr = d.k1 + 2.0 * d.k2 * r2 + 3.0 * d.k3 * (r2 * r2);                   // dg / dr2
-        const double g0 = 2.0 * (gr * y0 + d.p2), g1 = 2.0 * (gr * y1 + d.p1);               // dg / dy
-        const double f0 = (y0 * g + d.p2 * r2) - yd0, f1 = (y1 * g + d.p1 * r2) - yd1;
-        const double j00 = g + y0 * g0 + 2.0 * d.p2 * y0, j01 = y0 * g1 + 2.0 * d.p2 * y1;
-        const double j10 = y1 * g0 + 2.0 * d.p1 * y0, j11 = g + y1 * g1 + 2.0 * d.p1 * y1;
-        const double det = j00 * j11 - j01 * j10;
+        const LensJet jet = distort_jet(y0, y1, d);
+        const double det = jet.j00 * jet.j11 - jet.j01 * jet.j10;
         if (!(det > 0.0)) return false;
-        const double s0 = (j11 * f0 - j01 * f1) / det, s1 = (j00 * f1 - j10 * f0) / det;
+        const double f0 = jet.x - yd0, f1 = jet.y - yd1;
+        const double s0 = (jet.j11 * f0 - jet.j01 * f1) / det, s1 = (jet.j00 * f1 - jet.j10 * f0) / det;
         y0 -= s0;
         y1 -= s1;
         if (!(isfinite(y0) && isfinite(y1))) return false;
