@@ -751,6 +751,55 @@ int mpl_refine_cameras(const float *points, const float *pixels, const float *co
                        double *out_cams, double *out_error, double *out_cost0, double *out_cost, int *out_used, int *out_iterations,
                        unsigned char *out_status, void *stream);
 
+/* ---- locating cameras from scratch, csrc/locate_cameras.hip: robust resection.  mpl_refine_cameras starts from a pose that is
+ * nearly right; mpl_locate_cameras finds one where there is none, in the presence of wrong detections, by hypothesise-and-score: per
+ * view, `hypotheses` poses from six observations each, every one scored over all observations of the view.  Arguments, layouts and
+ * limits are those of mpl_refine_cameras.  Of a view's record only fx fy cx cy are read, and its lens row; the pose fields of a view
+ * that is not in fixed_mask are not looked at and may be NaN.  The reference has no such step.  One definition for the device and
+ * for the float64 restatement of the tests:
+ * 1. Participation is that of mpl_refine_cameras -- the weight finite and > 0, the pixel finite, the point finite -- and the pixel
+ *    goes back through the lens (the inverse above succeeds).  Slot n = b * joints + j, N = batch * joints.  The normalised
+ *    observation y = ((xu - cx) / fx, (yu - cy) / fy) of the undistorted pixel (xu, yu).
+ * 2. Per view, m = the mean of the participating points and s = 1 / sqrt(mean |X - m|^2 / 3), in fp64, summed in a fixed order; the
+ *    system is built on Xh = (s (X - m), 1).
+ * 3. Hypothesis h of view v draws six distinct participating slots: slot k, attempt a (0 .. 15) takes
+ *    n = floor(draw(keys[v], (h * 6 + k) * 16 + a) * N), draw the counter-based generator of mpl_synthesize_views; the first attempt
+ *    that participates and is not already chosen is kept; sixteen failures make the hypothesis void.  keys: HOST array of `views`
+ *    stream keys (Python: detrng._stream_key(seed, "locate_cameras", lane=v)).
+ * 4. The 12 x 12 system has the rows [Xh, 0, -y0 Xh] and [0, Xh, -y1 Xh] of the six samples; P (3 x 4, row-major) is its right
+ *    singular vector of the smallest singular value (a one-sided Jacobi on the system itself), with the sign that makes the summed
+ *    depth P_3 . Xh of the six samples positive.  Its left 3 x 3 block M = U S W^T gives R = U W^T, the column of the smallest
+ *    singular value turned over where det M < 0 so that det R = +1; scale = the mean singular value, t = P_4 / scale, and the centre
+ *    is c = m - R^T t / s.  Void: a singular value of M that is not > 0, a pose that is not finite, or a sample point at
+ *    z_cam <= 1e-9 under the pose.
+ * 5. The score of a hypothesis over all participating slots, with the projection of mpl_refine_cameras, lens included:
+ *    count = #{in front and |r|^2 <= threshold^2}, cost = sum w min(|r|^2, threshold^2), where a point that is not in front costs
+ *    w threshold^2; summed over the slots in their order, so the bits do not depend on the grid.  A void hypothesis scores (0, +inf).
+ * 6. The winner has the most inliers, then the lowest cost, then the lowest h.
+ * Outputs per view: out_cams (V,16), the intrinsics as given with the winner's pose; out_inliers (B,V,J) floats 0 / 1, the
+ * winner's within-threshold set; out_count (V) its size; out_best (V) the winner, -1 where every hypothesis is void; out_error (V)
+ * the plain root-mean-square of |r| in pixels over the inliers; out_status (V) bytes:
+ *   0 located;
+ *   2 passed through: bit v of fixed_mask is set; the record is returned bit for bit, out_best is -1, and inliers, count and error
+ *     are those of the given pose (count 0 and error NaN where it projects nothing within the threshold);
+ *   3 invalid: fewer than 6 observations take part, no hypothesis is valid, the winner has fewer than 6 inliers, or the intrinsics
+ *     are not finite; the record is returned as given, error is NaN, count 0 and the inliers 0.
+ * out_poses (V,hypotheses,12): R row-major, then the centre, NaN for a void hypothesis; out_scores (V,hypotheses,2): count, cost.
+ * Every hypothesis of a view that is fixed or has fewer than 6 participating observations is void.
+ * workspace: mpl_locate_cameras_workspace_bytes(batch, views, joints) device bytes (the participating observations of every view).
+ * Three launches -- observations, hypotheses (one lane each), winners --, fp64, no atomics, every sum in a fixed order: identical
+ * bits from run to run.  Stream-ordered, never synchronises; neither looks at nor sets the device error word.  out_cams may be
+ * cams_dev.
+ * MPL_E_INVALID: points, pixels, cams_dev, keys or an output NULL, a size that is not positive or beyond the limits;
+ * MPL_E_UNSUPPORTED: a threshold that is not finite and > 0, hypotheses outside [1, 65536]; MPL_E_WORKSPACE: no workspace or too
+ * small a one -- in this order, before any launch. */
+size_t mpl_locate_cameras_workspace_bytes(int batch, int views, int joints); /* 0 outside the limits */
+int mpl_locate_cameras(const float *points, const float *pixels, const float *conf, const double *cams_dev, const double *dist_dev,
+                       int batch, int views, int joints, double threshold, int hypotheses, const unsigned long long *keys,
+                       unsigned fixed_mask, void *workspace, size_t workspace_bytes, double *out_cams, float *out_inliers,
+                       int *out_count, int *out_best, double *out_error, unsigned char *out_status, double *out_poses,
+                       double *out_scores, void *stream);
+
 /* ---- Procrustes alignment of predicted poses onto their targets, csrc/procrustes.hip: the transform behind PA-MPJPE (Protocol
  * 2), in place of lib/utils/pose_utils.py:61-143 PoseUtils.procrustes (a numpy port of MATLAB's procrustes, one 3x3 SVD per pose
  * on the host, which would force all_preds back to the host).  One launch aligns `batch` poses: target A and prediction B, both

@@ -134,7 +134,9 @@ EXPORTS = ("mpl_hip_abi_version", "mpl_hip_error_string", "mpl_config_supported"
            # Levenberg-Marquardt on the reprojection error of 3D points, and the error itself; the reference has no such step
            "mpl_refine_points",
            # the transpose: Levenberg-Marquardt on the 6 pose unknowns of every camera, the points given; no counterpart either
-           "mpl_refine_cameras")
+           "mpl_refine_cameras",
+           # and the step before it: a camera located from scratch by hypothesise-and-score over 6-point resections
+           "mpl_locate_cameras_workspace_bytes", "mpl_locate_cameras")
 KINDS = ("spt", "row_stats", "gemm", "attention", "fuse_head", "pack")
 
 _lib = None
@@ -325,6 +327,11 @@ def load():
         lib.mpl_refine_cameras.restype = C.c_int
         lib.mpl_refine_cameras.argtypes = [_fp, _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, C.c_uint,
                                            _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp]
+        lib.mpl_locate_cameras_workspace_bytes.restype = C.c_size_t
+        lib.mpl_locate_cameras_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+        lib.mpl_locate_cameras.restype = C.c_int
+        lib.mpl_locate_cameras.argtypes = [_fp, _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.POINTER(C.c_uint64),
+                                           C.c_uint, _fp, C.c_size_t, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp]
         lib.mpl_procrustes_align.restype = C.c_int
         lib.mpl_procrustes_align.argtypes = [_fp, _fp, _fp, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int,
                                              C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, _fp]

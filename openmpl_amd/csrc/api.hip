@@ -956,6 +956,18 @@ int mpl_refine_cameras(const float* points, const float* pixels, const float* co
                                  (hipStream_t)stream);
 }
 
+size_t mpl_locate_cameras_workspace_bytes(int batch, int views, int joints) { return locate_cameras_workspace_bytes(batch, views, joints); }
+
+int mpl_locate_cameras(const float* points, const float* pixels, const float* conf, const double* cams_dev, const double* dist_dev,
+                       int batch, int views, int joints, double threshold, int hypotheses, const unsigned long long* keys,
+                       unsigned fixed_mask, void* workspace, size_t workspace_bytes, double* out_cams, float* out_inliers, int* out_count,
+                       int* out_best, double* out_error, unsigned char* out_status, double* out_poses, double* out_scores, void* stream) {
+    clear_stale_hip_error();
+    return launch_locate_cameras(points, pixels, conf, cams_dev, dist_dev, batch, views, joints, threshold, hypotheses, keys, fixed_mask,
+                                 workspace, workspace_bytes, out_cams, out_inliers, out_count, out_best, out_error, out_status, out_poses,
+                                 out_scores, (hipStream_t)stream);
+}
+
 int mpl_procrustes_align(const float* pred, const float* target, const float* conf, const int* sel, int n_sel, const float* scale3,
                          const float* offset3, int scaling, int reflection, int batch, int joints, float* aligned, float* d,
                          float* rotation, float* scale, float* translation, void* stream) {

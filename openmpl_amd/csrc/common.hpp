@@ -381,6 +381,14 @@ int launch_refine_cameras(const float* points, const float* pixels, const float*
                           double* out_cams, double* out_error, double* out_cost0, double* out_cost, int* out_used, int* out_iterations,
                           unsigned char* out_status, hipStream_t s);
 
+// locate_cameras.hip: robust resection of every view from known 3D points, hypothesise-and-score (mpl_locate_cameras); keys: host,
+// one detrng stream key per view
+size_t locate_cameras_workspace_bytes(int B, int V, int J);
+int launch_locate_cameras(const float* points, const float* pixels, const float* conf, const double* cams_dev, const double* dist_dev,
+                          int B, int V, int J, double threshold, int hypotheses, const unsigned long long* keys, unsigned fixed_mask,
+                          void* workspace, size_t workspace_bytes, double* out_cams, float* out_inliers, int* out_count, int* out_best,
+                          double* out_error, unsigned char* out_status, double* out_poses, double* out_scores, hipStream_t s);
+
 // synth.hip: model inputs synthesized from 3D poses (mpl_synthesize_views); dist_dev null: the pinhole kernel
 int launch_synthesize_views(const float* poses3d, const double* cams_dev, const double* dist_dev, const mpl_synth_options* opt, const float* conf,
                             const float* rotation_deg, const float* translation, const float* noise, const float* missing_u,

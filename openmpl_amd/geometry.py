@@ -10,7 +10,8 @@ triangulate_rays_robust (mpl_triangulate_robust, a third kernel) puts the view s
 and a pair consensus in front of the same least-squares fit.  refine_points / reprojection_errors (mpl_refine_points,
 csrc/refine.hip) work in the detector's unit: Levenberg-Marquardt on the reprojection error of a point in pixels, and that error for
 any 3D estimate.  refine_cameras (mpl_refine_cameras, csrc/refine_cameras.hip) is its transpose -- the points given, the camera poses
-moved --, and bundle_adjust alternates the two.
+moved --, and bundle_adjust alternates the two.  locate_cameras (mpl_locate_cameras, csrc/locate_cameras.hip) is the step before
+them: a camera located from no pose at all by hypothesise-and-score over 6-point resections.
 """
 from __future__ import annotations
 
@@ -330,6 +331,94 @@ def refine_cameras(points: torch.Tensor, pixels: torch.Tensor, conf: Optional[to
     V = pixels.shape[1] if isinstance(pixels, torch.Tensor) and pixels.ndim == 4 else 0
     mask = _fixed_mask(fixed, V) if V else 0             # a pixels tensor of another form is _observations' to complain about
     return _refine_cameras(points, pixels, conf, cams, distortion, h, max_iterations, tol, mask)
+
+
+class CamerasLocated(NamedTuple):
+    """what locate_cameras returns"""
+    cams: torch.Tensor            # (V,16) float64: the records with the located (refine=True: polished) poses, intrinsics as given
+    inliers: torch.Tensor         # (B,V,J) float32, 0 / 1: the observations within the threshold of the winning hypothesis
+    count: torch.Tensor           # (V,) int32: how many
+    best: torch.Tensor            # (V,) int32: the winning hypothesis, -1 where there is none
+    error: torch.Tensor           # (V,) float64: the plain root-mean-square of |r| over the inliers, pixels
+    status: torch.Tensor          # (V,) uint8: 0 located, 2 passed through, 3 invalid
+    refined: Optional[CamerasRefined]    # the polish; None without refine=True
+    poses: Optional[torch.Tensor]        # (V,H,12) float64: R row-major, then the centre; None without return_hypotheses=True
+    scores: Optional[torch.Tensor]       # (V,H,2) float64: count, cost
+
+
+def locate_cameras(points: torch.Tensor, pixels: torch.Tensor, conf: Optional[torch.Tensor], cams: torch.Tensor,
+                   distortion: Optional[torch.Tensor] = None, threshold: float = 6.0, hypotheses: int = 1024, seed: int = 0,
+                   fixed: Sequence[int] = (), refine: bool = False, huber: Optional[float] = None,
+                   return_hypotheses: bool = False) -> CamerasLocated:
+    """Cameras located from scratch: the step from no pose at all into the basin of refine_cameras, in the presence of wrong
+    detections.  points (B,J,3), pixels (B,V,J,2), conf (B,V,J) or None, cams (V,16) float64 and distortion (V,5) or None are the
+    arguments of refine_cameras, but of a view's record only fx fy cx cy and its lens row are read: the pose fields of a view that
+    is not in `fixed` are not looked at and may be NaN.  -> CamerasLocated(cams, inliers, count, best, error, status, refined,
+    poses, scores), one entry per view.
+
+    Per view, `hypotheses` (1 .. 65536) poses are formed, each the 6-point DLT of six participating observations drawn with the
+    counter-based generator of synthesize_views under `seed`, and each is scored over all participating observations by its
+    reprojection error in pixels, lens included: count = the observations within `threshold` (pixels, finite and > 0), cost = sum w
+    min(|r|^2, threshold^2).  The winner has the most inliers, then the lowest cost, then the lowest number (include/mpl_hip.h has
+    the six steps).  An observation takes part as in refine_cameras, and its pixel has to go back through the lens.
+
+    Located (status 0): the record carries the winner's pose.  Passed through (2): the view is in `fixed`; its record is returned
+    bit for bit, inliers, count and error are those of the given pose.  Invalid (3): fewer than 6 observations take part, no
+    hypothesis is valid, the winner has fewer than 6 inliers or the intrinsics are not finite; the record is returned as given, error
+    is NaN, count 0 and the inliers 0.  A winner is a start, not a fit: from 136 observations with 2 px of noise and a quarter of
+    them planted 40 to 120 px off it lies within a few degrees and tenths of a unit.  refine=True adds one launch, the polish:
+    refine_cameras(points, pixels, conf * inliers (inliers with conf=None), cams, distortion, huber=huber, fixed=fixed), whose
+    records become `cams` and which is returned whole as `refined`; inliers, count, best and error stay those of the hypothesis
+    stage.  `huber` without `refine` raises.  Below about 68 observations of a view the result follows the noise, as that of
+    refine_cameras does.  return_hypotheses=True hands out every hypothesis: poses (V,H,12), NaN where void, and scores (V,H,2),
+    (0, inf) where void.
+
+    The recipe for a rig of which two cameras are calibrated: triangulate_pixels with those two views -> locate_cameras(fixed=(0, 1),
+    refine=True) -> bundle_adjust(fixed=(0, 1)).  Three launches before the polish, no synchronisation, nothing read back, identical
+    bits from run to run."""
+    from . import detrng
+    if huber is not None and not refine:
+        raise RuntimeError("huber is an option of the refinement: it needs refine=True")
+    h = _refine_options(huber, 20, 1e-8)[0]
+    try:
+        tau = float(threshold)
+    except (TypeError, ValueError):
+        tau = math.nan
+    if not (tau > 0.0 and math.isfinite(tau)):
+        raise RuntimeError("threshold must be a positive finite number of pixels (got %r)" % (threshold,))
+    try:
+        H = -1 if isinstance(hypotheses, bool) else operator.index(hypotheses)
+    except TypeError:
+        H = -1
+    if not 1 <= H <= 65536:
+        raise RuntimeError("hypotheses must be an integer in [1, 65536] (got %r)" % (hypotheses,))
+    try:
+        seed = -1 if isinstance(seed, bool) else operator.index(seed)
+    except TypeError:
+        raise RuntimeError("seed must be an integer (got %r)" % (seed,))
+    V = pixels.shape[1] if isinstance(pixels, torch.Tensor) and pixels.ndim == 4 else 0
+    mask = _fixed_mask(fixed, V) if V else 0             # a pixels tensor of another form is _observations' to complain about
+    (points, pixels, conf), cams, distortion, B, V, J = _observations(points, pixels, conf, cams, distortion)
+    dev = pixels.device
+    keys = (cabi.C.c_uint64 * V)(*(int(detrng._stream_key(seed, "locate_cameras", lane=v)) for v in range(V)))
+    ws = torch.empty((cabi.load().mpl_locate_cameras_workspace_bytes(B, V, J),), dtype=torch.uint8, device=dev)
+    out_cams = torch.empty((V, 16), dtype=torch.float64, device=dev)
+    inliers = torch.empty((B, V, J), dtype=torch.float32, device=dev)
+    count = torch.empty((V,), dtype=torch.int32, device=dev)
+    best = torch.empty((V,), dtype=torch.int32, device=dev)
+    error = torch.empty((V,), dtype=torch.float64, device=dev)
+    status = torch.empty((V,), dtype=torch.uint8, device=dev)
+    poses = torch.empty((V, H, 12), dtype=torch.float64, device=dev)
+    scores = torch.empty((V, H, 2), dtype=torch.float64, device=dev)
+    cabi.launch("locate_cameras", dev, points.data_ptr(), pixels.data_ptr(), ptr(conf), cams.data_ptr(), ptr(distortion), B, V, J, tau, H,
+                keys, mask, ws.data_ptr(), ws.numel(), out_cams.data_ptr(), inliers.data_ptr(), count.data_ptr(), best.data_ptr(),
+                error.data_ptr(), status.data_ptr(), poses.data_ptr(), scores.data_ptr())
+    refined = None
+    if refine:
+        refined = _refine_cameras(points, pixels, inliers if conf is None else conf * inliers, out_cams, distortion, h, 20, 1e-8, mask)
+        out_cams = refined.cams
+    return CamerasLocated(out_cams, inliers, count, best, error, status, refined, poses if return_hypotheses else None,
+                          scores if return_hypotheses else None)
 
 
 def bundle_adjust(points: torch.Tensor, pixels: torch.Tensor, conf: Optional[torch.Tensor], cams: torch.Tensor,
