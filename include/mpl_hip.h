@@ -800,6 +800,102 @@ int mpl_locate_cameras(const float *points, const float *pixels, const float *co
                        int *out_count, int *out_best, double *out_error, unsigned char *out_status, double *out_poses,
                        double *out_scores, void *stream);
 
+/* ---- the relative pose of two views from their detections alone, csrc/relative_pose.hip with csrc/five_point.hpp: robust
+ * five-point solver.  mpl_locate_cameras needs 3D points; mpl_relative_pose is the step before it, for a rig of which nothing is
+ * known but the intrinsics: per pair of views (a, b), `hypotheses` five-point solutions, every candidate scored over all
+ * correspondences of the pair.  pixels (B,V,J,2), conf (B,V,J) or NULL, cams_dev (V,16) -- only fx fy cx cy are read, the pose
+ * fields may be NaN --, dist_dev (V,5) or NULL; pairs: HOST array (n_pairs,2) of view indices, a != b, n_pairs <= MPL_MAX_VIEWS;
+ * views <= MPL_MAX_VIEWS, joints <= 64, batch * views * joints and batch * n_pairs * joints <= 2^30.  The convention is
+ * x_b = R x_a + t with |t| = 1 (the length of the baseline cannot be seen).  The reference has no such step.  One definition for
+ * the device and for the float64 restatement of the tests:
+ * 1. Slot n = b * joints + j, N = batch * joints.  It takes part in pair (a, b) when in both views the weight is finite and > 0,
+ *    the pixel is finite and goes back through the lens (the inverse above succeeds), and both views' intrinsics are finite.  Its
+ *    weight is w = conf_a * conf_b (1 without conf); u_a, u_b are the undistorted pixels, y = ((u0 - cx) / fx, (u1 - cy) / fy) their
+ *    normalised coordinates.  A pair is usable with at least 5 participating slots.
+ * 2. Hypothesis h of pair p draws five distinct participating slots by the scheme of step 3 of mpl_locate_cameras: slot k, attempt a
+ *    (0 .. 15) takes n = floor(draw(keys[p], (h * 5 + k) * 16 + a) * N); the first attempt that participates and is not already
+ *    chosen is kept; sixteen failures make the hypothesis void.  keys: HOST array of n_pairs stream keys (Python:
+ *    detrng._stream_key(seed, "relative_pose", lane=p)).
+ * 3. The candidates are all real E with d_b^T E d_a = 0 on the five samples (d = (y0, y1, 1)), det E = 0 and
+ *    2 E E^T E - tr(E E^T) E = 0.  The 5 x 9 system has the rows kron(d_b, d_a); its null space comes from a one-sided Jacobi on
+ *    the system itself (the four shortest columns of A V), and X, Y, Z, W of E = x X + y Y + z Z + W are the columns of the
+ *    projector on it at the four largest entries of its diagonal (descending, the lowest index among equals), made orthonormal in
+ *    that order by Gram-Schmidt with every projection taken twice: a basis that does not depend on how the null space was found.
+ *    The ten cubics in the 20 monomials of degree <= 3
+ *    are eliminated by Gauss-Jordan with partial pivoting on the columns x^3 y^3 x^2y xy^2 x^2z x^2 y^2z y^2 xyz xy; the rows
+ *    <x^2 z> - z <x^2>, <y^2 z> - z <y^2>, <xyz> - z <xy> form a 3 x 3 polynomial matrix B(z) with B(z) (x, y, 1)^T = 0 (Nister).
+ *    The real roots of det B(z), of degree 10, are counted and isolated by a Sturm chain, bisected and polished by Newton, in
+ *    ascending order; (x, y, 1) is the cross product of the two rows of B(z) that make the longest one, and (x, y, z) is then
+ *    polished by three Gauss-Newton steps on the ten cubics themselves (B(z) loses its rank by two where two candidates have
+ *    nearly the same z).  `roots` of a hypothesis is the number of real roots.
+ *    The pose of a candidate: E = U diag(s) V^T by the 3 x 3 Jacobi of mpl_locate_cameras with U, V
+ *    proper, R in {U W V^T, U W^T V^T}, t = +-u_3, in that order; the first combination that puts all five samples at a depth
+ *    > 1e-9 in both cameras is kept, the depths (l_a, l_b) of l_a R d_a - l_b d_b = -t by its 2 x 2 normal equations; none doing so
+ *    makes the candidate void.
+ * 4. The score of a candidate over all participating slots in their order: the signed Sampson distance in pixels on the
+ *    undistorted pixels, d = u_b^T F u_a / sqrt((F u_a)_0^2 + (F u_a)_1^2 + (F^T u_b)_0^2 + (F^T u_b)_1^2) with
+ *    F = K_b^-T [t]x R K_a^-1; count = #{d^2 <= threshold^2}, cost = sum w min(d^2, threshold^2).  A hypothesis keeps its best
+ *    candidate: most inliers, then the lowest cost, then the lowest root.  A hypothesis without a valid candidate scores (0, +inf).
+ * 5. The winner has the most inliers, then the lowest cost, then the lowest h.
+ * The draws are keyed by the pair's index p, not by its views: the pairs (0,1) and (1,0) of one call draw different samples, and
+ * only as pair 0 of a call each do they see the same hypotheses (then R_10 = R_01^T, t_10 = -R_01^T t_01 hypothesis by hypothesis).
+ * Outputs per pair: out_rotation (P,3,3) row-major and out_direction (P,3), the winner's R and t; out_cams (P,2,16): record 0 is
+ * view a with R = I and centre 0, record 1 is view b with R and the centre -baseline * R^T t, the intrinsics as given;
+ * out_inliers (B,P,J) floats 0 / 1, the winner's within-threshold set; out_count (P) its size; out_best (P) the winner, -1 where
+ * every hypothesis is void; out_error (P) the root-mean-square of |d| in pixels over the inliers; out_status (P) bytes:
+ *   0 located: the winner has at least 6 inliers, one more than a sample fits by construction;
+ *   3 invalid: fewer than 5 slots take part, no hypothesis is valid, the winner has fewer than 6 inliers, or the intrinsics of a
+ *     view are not finite; rotation, direction and the pose fields of both records are NaN, error is NaN, count 0, the inliers 0.
+ * out_poses (P,hypotheses,12): R row-major, then t, NaN for a void hypothesis; out_scores (P,hypotheses,2): count, cost;
+ * out_roots (P,hypotheses) ints.
+ * workspace: mpl_relative_pose_workspace_bytes(batch, n_pairs, joints) device bytes (the correspondences of every pair).
+ * Three launches -- correspondences, hypotheses (one lane each), winners --, fp64, no atomics, every sum in a fixed order:
+ * identical bits from run to run.  Stream-ordered, never synchronises; neither looks at nor sets the device error word.
+ * MPL_E_INVALID: pixels, cams_dev, pairs, keys or an output NULL, a size that is not positive or beyond the limits, a pair that is
+ * not two distinct views; MPL_E_UNSUPPORTED: a threshold or a baseline that is not finite and > 0, hypotheses outside [1, 65536];
+ * MPL_E_WORKSPACE: no workspace or too small a one -- in this order, before any launch. */
+size_t mpl_relative_pose_workspace_bytes(int batch, int pairs, int joints); /* 0 outside the limits */
+int mpl_relative_pose(const float *pixels, const float *conf, const double *cams_dev, const double *dist_dev, int batch, int views,
+                      int joints, const int *pairs, int n_pairs, double threshold, int hypotheses, const unsigned long long *keys,
+                      double baseline, void *workspace, size_t workspace_bytes, double *out_rotation, double *out_direction,
+                      double *out_cams, float *out_inliers, int *out_count, int *out_best, double *out_error,
+                      unsigned char *out_status, double *out_poses, double *out_scores, int *out_roots, void *stream);
+
+/* ---- the polish of a relative pose, csrc/refine_relative_pose.hip: Levenberg-Marquardt on the 5 unknowns of (R, t), |t| = 1, over
+ * the signed Sampson distances d of step 4 of mpl_relative_pose, from the pose it is given (rotation (P,3,3), direction (P,3)).  It is
+ * the loop of mpl_refine_cameras -- lambda from 1e-3, divided by 10 after a trial that lowers the cost strictly and multiplied by 10
+ * after one that does not, the statuses, the limits -- on E(R, t) = sum w rho(d^2), rho plain or Huber as in mpl_refine_points
+ * (huber in pixels; <= 0 or NaN: plain).  Alternating bundle adjustment is no substitute: it crawls along the two-view valley.
+ * Participation and weights: those of step 1 of mpl_relative_pose, w = conf_a * conf_b, times weight[b, p, j] where `weight` (B,P,J)
+ * is given (finite and > 0 to take part): the inlier mask of mpl_relative_pose is such a tensor.  conf, weight, dist_dev may be NULL.
+ * Trial: R' = exp([w]x) R (Rodrigues, as mpl_refine_cameras), t' = normalise(t + d1 e1 + d2 e2), delta = (w, d1, d2); e1 =
+ * normalise(t x axis_k) with k the coordinate of t of the smallest magnitude (the lowest among equals), e2 = t x e1.
+ * Jacobian, analytic: with a = K_a^-1 u_a, b = K_b^-1 u_b and E = [t]x R, d = n / s, n = b^T E a, s^2 = (E a)_0^2 / fx_b^2 +
+ * (E a)_1^2 / fy_b^2 + (E^T b)_0^2 / fx_a^2 + (E^T b)_1^2 / fy_a^2 = |g|^2; along a direction E' of E the derivative is
+ * n' / s - n (g . g') / s^3; the five directions are [t]x [e_k]x R (k = 0, 1, 2), [e1]x R and [e2]x R.  H = sum w' J J^T,
+ * g = sum w' J d with the IRLS weights; (H + lambda diag H) delta = -g by an unpivoted Cholesky factorisation.
+ * After a trial, accepted or not: converged when max |delta| <= step_tolerance; else capped when lambda > 1e12 or after
+ * max_iterations trials.
+ * Outputs per pair: out_rotation, out_direction the final pose; out_cams (P,2,16) the two records of mpl_relative_pose under it;
+ * out_error = sqrt(sum w d^2 / sum w) there, in both modes; out_cost0, out_cost = E at the given and the final pose, out_cost <=
+ * out_cost0; out_used the correspondences that take part; out_iterations the trials; out_status bytes:
+ *   0 converged;  1 capped;
+ *   2 passed through: max_iterations == 0 or fewer than 6 correspondences take part; the pose is returned bit for bit, error and
+ *     costs are computed, out_cost == out_cost0;
+ *   3 invalid: the given pose or the intrinsics are not finite, or nothing takes part; the pose is returned as given, the pose fields
+ *     of the records, error and costs are NaN.
+ * out_cost0, out_cost, out_used, out_iterations, out_status may be NULL.  One launch, one workgroup per pair, fp64 sums in a fixed
+ * order, no atomics: identical bits from run to run.  Stream-ordered, never synchronises.
+ * MPL_E_INVALID: pixels, cams_dev, pairs, rotation, direction or one of the first four outputs NULL, a size beyond the limits of
+ * mpl_relative_pose, a pair that is not two distinct views; MPL_E_UNSUPPORTED: max_iterations outside [0, 1000], a step_tolerance
+ * that is negative or not finite, a baseline that is not finite and > 0 -- before any launch. */
+int mpl_refine_relative_pose(const float *pixels, const float *conf, const float *weight, const double *cams_dev,
+                             const double *dist_dev, int batch, int views, int joints, const int *pairs, int n_pairs,
+                             const double *rotation, const double *direction, double huber, int max_iterations,
+                             double step_tolerance, double baseline, double *out_rotation, double *out_direction, double *out_cams,
+                             double *out_error, double *out_cost0, double *out_cost, int *out_used, int *out_iterations,
+                             unsigned char *out_status, void *stream);
+
 /* ---- Procrustes alignment of predicted poses onto their targets, csrc/procrustes.hip: the transform behind PA-MPJPE (Protocol
  * 2), in place of lib/utils/pose_utils.py:61-143 PoseUtils.procrustes (a numpy port of MATLAB's procrustes, one 3x3 SVD per pose
  * on the host, which would force all_preds back to the host).  One launch aligns `batch` poses: target A and prediction B, both

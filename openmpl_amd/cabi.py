@@ -136,7 +136,11 @@ EXPORTS = ("mpl_hip_abi_version", "mpl_hip_error_string", "mpl_config_supported"
            # the transpose: Levenberg-Marquardt on the 6 pose unknowns of every camera, the points given; no counterpart either
            "mpl_refine_cameras",
            # and the step before it: a camera located from scratch by hypothesise-and-score over 6-point resections
-           "mpl_locate_cameras_workspace_bytes", "mpl_locate_cameras")
+           "mpl_locate_cameras_workspace_bytes", "mpl_locate_cameras",
+           # and the step before that one: the relative pose of two views from their detections alone, by five-point hypotheses
+           "mpl_relative_pose_workspace_bytes", "mpl_relative_pose",
+           # and its polish: Levenberg-Marquardt on the 5 unknowns of (R, t) over the Sampson distances of the pair
+           "mpl_refine_relative_pose")
 KINDS = ("spt", "row_stats", "gemm", "attention", "fuse_head", "pack")
 
 _lib = None
@@ -332,6 +336,16 @@ def load():
         lib.mpl_locate_cameras.restype = C.c_int
         lib.mpl_locate_cameras.argtypes = [_fp, _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.POINTER(C.c_uint64),
                                            C.c_uint, _fp, C.c_size_t, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp]
+        lib.mpl_relative_pose_workspace_bytes.restype = C.c_size_t
+        lib.mpl_relative_pose_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+        lib.mpl_relative_pose.restype = C.c_int
+        lib.mpl_relative_pose.argtypes = [_fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_double, C.c_int,
+                                          C.POINTER(C.c_uint64), C.c_double, _fp, C.c_size_t, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp,
+                                          _fp, _fp, _fp]
+        lib.mpl_refine_relative_pose.restype = C.c_int
+        lib.mpl_refine_relative_pose.argtypes = [_fp, _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, _fp, _fp,
+                                                 C.c_double, C.c_int, C.c_double, C.c_double, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp,
+                                                 _fp]
         lib.mpl_procrustes_align.restype = C.c_int
         lib.mpl_procrustes_align.argtypes = [_fp, _fp, _fp, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int,
                                              C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, _fp]

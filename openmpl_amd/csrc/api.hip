@@ -968,6 +968,30 @@ int mpl_locate_cameras(const float* points, const float* pixels, const float* co
                                  out_scores, (hipStream_t)stream);
 }
 
+size_t mpl_relative_pose_workspace_bytes(int batch, int pairs, int joints) { return relative_pose_workspace_bytes(batch, pairs, joints); }
+
+int mpl_relative_pose(const float* pixels, const float* conf, const double* cams_dev, const double* dist_dev, int batch, int views,
+                      int joints, const int* pairs, int n_pairs, double threshold, int hypotheses, const unsigned long long* keys,
+                      double baseline, void* workspace, size_t workspace_bytes, double* out_rotation, double* out_direction,
+                      double* out_cams, float* out_inliers, int* out_count, int* out_best, double* out_error, unsigned char* out_status,
+                      double* out_poses, double* out_scores, int* out_roots, void* stream) {
+    clear_stale_hip_error();
+    return launch_relative_pose(pixels, conf, cams_dev, dist_dev, batch, views, joints, pairs, n_pairs, threshold, hypotheses, keys,
+                                baseline, workspace, workspace_bytes, out_rotation, out_direction, out_cams, out_inliers, out_count,
+                                out_best, out_error, out_status, out_poses, out_scores, out_roots, (hipStream_t)stream);
+}
+
+int mpl_refine_relative_pose(const float* pixels, const float* conf, const float* weight, const double* cams_dev, const double* dist_dev,
+                             int batch, int views, int joints, const int* pairs, int n_pairs, const double* rotation,
+                             const double* direction, double huber, int max_iterations, double step_tolerance, double baseline,
+                             double* out_rotation, double* out_direction, double* out_cams, double* out_error, double* out_cost0,
+                             double* out_cost, int* out_used, int* out_iterations, unsigned char* out_status, void* stream) {
+    clear_stale_hip_error();
+    return launch_refine_relative_pose(pixels, conf, weight, cams_dev, dist_dev, batch, views, joints, pairs, n_pairs, rotation, direction,
+                                       huber, max_iterations, step_tolerance, baseline, out_rotation, out_direction, out_cams, out_error,
+                                       out_cost0, out_cost, out_used, out_iterations, out_status, (hipStream_t)stream);
+}
+
 int mpl_procrustes_align(const float* pred, const float* target, const float* conf, const int* sel, int n_sel, const float* scale3,
                          const float* offset3, int scaling, int reflection, int batch, int joints, float* aligned, float* d,
                          float* rotation, float* scale, float* translation, void* stream) {

@@ -389,6 +389,23 @@ int launch_locate_cameras(const float* points, const float* pixels, const float*
                           void* workspace, size_t workspace_bytes, double* out_cams, float* out_inliers, int* out_count, int* out_best,
                           double* out_error, unsigned char* out_status, double* out_poses, double* out_scores, hipStream_t s);
 
+// relative_pose.hip: the relative pose of pairs of views from their detections alone, hypothesise-and-score over five-point
+// solutions (mpl_relative_pose); pairs: host (P,2) view indices, keys: host, one detrng stream key per pair
+size_t relative_pose_workspace_bytes(int B, int P, int J);
+int launch_relative_pose(const float* pixels, const float* conf, const double* cams_dev, const double* dist_dev, int B, int V, int J,
+                         const int* pairs, int P, double threshold, int hypotheses, const unsigned long long* keys, double baseline,
+                         void* workspace, size_t workspace_bytes, double* out_rotation, double* out_direction, double* out_cams,
+                         float* out_inliers, int* out_count, int* out_best, double* out_error, unsigned char* out_status, double* out_poses,
+                         double* out_scores, int* out_roots, hipStream_t s);
+
+// refine_relative_pose.hip: Levenberg-Marquardt on the 5 unknowns of a relative pose over the Sampson distances of its pair, one
+// workgroup per pair (mpl_refine_relative_pose)
+int launch_refine_relative_pose(const float* pixels, const float* conf, const float* weight, const double* cams_dev, const double* dist_dev,
+                                int B, int V, int J, const int* pairs, int P, const double* rotation, const double* direction, double huber,
+                                int max_iterations, double step_tolerance, double baseline, double* out_rotation, double* out_direction,
+                                double* out_cams, double* out_error, double* out_cost0, double* out_cost, int* out_used, int* out_iterations,
+                                unsigned char* out_status, hipStream_t s);
+
 // synth.hip: model inputs synthesized from 3D poses (mpl_synthesize_views); dist_dev null: the pinhole kernel
 int launch_synthesize_views(const float* poses3d, const double* cams_dev, const double* dist_dev, const mpl_synth_options* opt, const float* conf,
                             const float* rotation_deg, const float* translation, const float* noise, const float* missing_u,

@@ -11,7 +11,9 @@ and a pair consensus in front of the same least-squares fit.  refine_points / re
 csrc/refine.hip) work in the detector's unit: Levenberg-Marquardt on the reprojection error of a point in pixels, and that error for
 any 3D estimate.  refine_cameras (mpl_refine_cameras, csrc/refine_cameras.hip) is its transpose -- the points given, the camera poses
 moved --, and bundle_adjust alternates the two.  locate_cameras (mpl_locate_cameras, csrc/locate_cameras.hip) is the step before
-them: a camera located from no pose at all by hypothesise-and-score over 6-point resections.
+them: a camera located from no pose at all by hypothesise-and-score over 6-point resections.  relative_pose (mpl_relative_pose,
+csrc/relative_pose.hip) is the step before that one: the relative pose of two views from their detections and intrinsics alone, by
+hypothesise-and-score over five-point solutions.
 """
 from __future__ import annotations
 
@@ -170,17 +172,19 @@ class Refined(NamedTuple):
     status: torch.Tensor          # (B,J) uint8: 0 converged, 1 capped, 2 passed through, 3 invalid
 
 
-def _observations(points, pixels, conf, cams, distortion):
+def _observations(points, pixels, conf, cams, distortion, with_points=True):
     """The argument checks of refine_points in the order of _lines: shapes first, then dtypes, then devices, each complaint naming
-    its argument and raised before any device is touched; cams and distortion as prepare_inputs checks them."""
+    its argument and raised before any device is touched; cams and distortion as prepare_inputs checks them.  with_points=False (the
+    call that knows no points: relative_pose) leaves the points out of the checks and of the returned list."""
     from .inputs import check_distortion
-    for what, t in (("points", points), ("pixels", pixels)) + ((("conf", conf),) if conf is not None else ()):
+    for what, t in ((("points", points),) if with_points else ()) + (("pixels", pixels),) + ((("conf", conf),) if conf is not None else ()):
         if not isinstance(t, torch.Tensor):
             raise RuntimeError("%s must be a tensor" % what)
     if pixels.ndim != 4 or pixels.shape[3] != 2 or min(pixels.shape[:3]) < 1:
         raise RuntimeError("pixels: expected shape (B,V,J,2), got %s" % (tuple(pixels.shape),))
     B, V, J, _ = pixels.shape
-    groups = [("points", points, (B, J, 3)), ("pixels", pixels, (B, V, J, 2))] + ([("conf", conf, (B, V, J))] if conf is not None else [])
+    groups = ([("points", points, (B, J, 3))] if with_points else []) + [("pixels", pixels, (B, V, J, 2))] + \
+        ([("conf", conf, (B, V, J))] if conf is not None else [])
     for what, t, shape in groups:
         if tuple(t.shape) != shape:
             raise RuntimeError("%s: expected shape %s, got %s" % (what, shape, tuple(t.shape)))
@@ -419,6 +423,191 @@ def locate_cameras(points: torch.Tensor, pixels: torch.Tensor, conf: Optional[to
         out_cams = refined.cams
     return CamerasLocated(out_cams, inliers, count, best, error, status, refined, poses if return_hypotheses else None,
                           scores if return_hypotheses else None)
+
+
+class RelativeRefined(NamedTuple):
+    """what refine_relative_pose returns"""
+    rotation: torch.Tensor        # (P,3,3) float64
+    direction: torch.Tensor       # (P,3) float64, of unit length
+    cams: torch.Tensor            # (P,2,16) float64: the two records of relative_pose under the final pose
+    error: torch.Tensor           # (P,) float64: the weighted root-mean-square Sampson distance at the final pose, pixels
+    cost0: torch.Tensor           # (P,) float64: E at the given pose, in the mode of the call
+    cost: torch.Tensor            # (P,) float64: E at the final pose; never above cost0
+    used: torch.Tensor            # (P,) int32: correspondences that take part
+    iterations: torch.Tensor      # (P,) int32: trial steps made
+    status: torch.Tensor          # (P,) uint8: 0 converged, 1 capped, 2 passed through, 3 invalid
+
+
+class RelativePose(NamedTuple):
+    """what relative_pose returns"""
+    rotation: torch.Tensor        # (P,3,3) float64: R of x_b = R x_a + t, NaN where the pair is invalid
+    direction: torch.Tensor       # (P,3) float64: t, of unit length
+    cams: torch.Tensor            # (P,2,16) float64: view a as the gauge (R = I, centre 0), view b at -baseline R^T t; intrinsics as given
+    inliers: torch.Tensor         # (B,P,J) float32, 0 / 1: the correspondences within the threshold of the winning hypothesis
+    count: torch.Tensor           # (P,) int32: how many
+    best: torch.Tensor            # (P,) int32: the winning hypothesis, -1 where there is none
+    error: torch.Tensor           # (P,) float64: the root-mean-square Sampson distance over the inliers, pixels
+    status: torch.Tensor          # (P,) uint8: 0 located, 3 invalid
+    refined: Optional["RelativeRefined"]     # the polish; None without refine=True
+    poses: Optional[torch.Tensor]        # (P,H,12) float64: R row-major, then t; None without return_hypotheses=True
+    scores: Optional[torch.Tensor]       # (P,H,2) float64: count, cost
+    roots: Optional[torch.Tensor]        # (P,H) int32: the real candidates of every hypothesis
+
+
+def _pairs(pairs, V):
+    """`pairs`, a sequence of (a, b) with a != b view indices in 0 .. V-1 -> a flat list of ints"""
+    try:
+        pairs = [tuple(p) for p in pairs]
+    except TypeError:
+        raise RuntimeError("pairs must be a sequence of (a, b) view indices (got %r)" % (pairs,))
+    if not 1 <= len(pairs) <= cabi.MPL_MAX_VIEWS:
+        raise RuntimeError("between 1 and %d pairs (got %d)" % (cabi.MPL_MAX_VIEWS, len(pairs)))
+    flat = []
+    for p in pairs:
+        idx = []
+        for v in p:
+            try:
+                idx.append(-1 if isinstance(v, bool) else operator.index(v))
+            except TypeError:
+                idx.append(-1)
+        if len(idx) != 2 or not all(0 <= i < V for i in idx) or idx[0] == idx[1]:
+            raise RuntimeError("pairs holds two distinct view indices, integers in [0, %d] (got %r)" % (V - 1, p))
+        flat += idx
+    return flat
+
+
+def _baseline(baseline):
+    try:
+        base = float(baseline)
+    except (TypeError, ValueError):
+        base = math.nan
+    if not (base > 0.0 and math.isfinite(base)):
+        raise RuntimeError("baseline must be a positive finite length (got %r)" % (baseline,))
+    return base
+
+
+def _refine_relative(pixels, conf, weight, cams, flat, rotation, direction, distortion, h, max_iterations, tol, base):
+    (pixels, conf), cams, distortion, B, V, J = _observations(None, pixels, conf, cams, distortion, with_points=False)
+    dev = pixels.device
+    P = len(flat) // 2
+    for what, t, shape, dt in (("rotation", rotation, (P, 3, 3), torch.float64), ("direction", direction, (P, 3), torch.float64)) + \
+            ((("weight", weight, (B, P, J), torch.float32),) if weight is not None else ()):
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != dt or t.device != dev:
+            raise RuntimeError("%s must be %s %s on the device of pixels" % (what, str(dt).replace("torch.", ""), shape))
+    f64 = dict(dtype=torch.float64, device=dev)
+    i32 = dict(dtype=torch.int32, device=dev)
+    out = RelativeRefined(torch.empty((P, 3, 3), **f64), torch.empty((P, 3), **f64), torch.empty((P, 2, 16), **f64), torch.empty((P,), **f64),
+                          torch.empty((P,), **f64), torch.empty((P,), **f64), torch.empty((P,), **i32), torch.empty((P,), **i32),
+                          torch.empty((P,), dtype=torch.uint8, device=dev))
+    cabi.launch("refine_relative_pose", dev, pixels.data_ptr(), ptr(conf), ptr(None if weight is None else weight.contiguous()),
+                cams.data_ptr(), ptr(distortion), B, V, J, (cabi.C.c_int * len(flat))(*flat), P, rotation.contiguous().data_ptr(),
+                direction.contiguous().data_ptr(), h, max_iterations, tol, base, *(t.data_ptr() for t in out))
+    return out
+
+
+def refine_relative_pose(pixels: torch.Tensor, conf: Optional[torch.Tensor], cams: torch.Tensor, pairs: Sequence[Tuple[int, int]],
+                         rotation: torch.Tensor, direction: torch.Tensor, distortion: Optional[torch.Tensor] = None,
+                         huber: Optional[float] = None, max_iterations: int = 20, step_tolerance: float = 1e-8, baseline: float = 1.0,
+                         weight: Optional[torch.Tensor] = None) -> RelativeRefined:
+    """The polish of relative_pose: rotation (P,3,3) and direction (P,3) float64 of x_b = R x_a + t moved to the minimum of
+    E(R, t) = sum w rho(d^2), d the signed Sampson distance in pixels of a correspondence on the undistorted pixels, by
+    Levenberg-Marquardt on the 5 unknowns (a rotation, and t on the unit sphere) from the given pose.  pixels, conf, cams, pairs and
+    distortion are the arguments of relative_pose; w = conf_a * conf_b, times `weight` (B,P,J) float32 where given -- the inlier
+    mask of relative_pose is such a tensor, and a correspondence whose weight is not finite and > 0 takes no part.  `huber` as in
+    refine_points.  -> RelativeRefined(rotation, direction, cams, error, cost0, cost, used, iterations, status), one entry per pair.
+
+    A trial is accepted only if it lowers E, so cost <= cost0.  Converged (status 0) when the step is <= step_tolerance, else capped
+    (1) after `max_iterations` trials (0 .. 1000).  Passed through (2): max_iterations == 0 or fewer than 6 correspondences take
+    part; the pose is returned bit for bit, error and costs are computed.  Invalid (3): the given pose or the intrinsics are not
+    finite, or nothing takes part; the pose is returned as given, the records' poses, error and costs are NaN.  One launch, one
+    workgroup per pair, no synchronisation, identical bits from run to run."""
+    h, max_iterations, tol = _refine_options(huber, max_iterations, step_tolerance)
+    base = _baseline(baseline)
+    V = pixels.shape[1] if isinstance(pixels, torch.Tensor) and pixels.ndim == 4 else 0
+    flat = _pairs(pairs, V) if V else []
+    return _refine_relative(pixels, conf, weight, cams, flat, rotation, direction, distortion, h, max_iterations, tol, base)
+
+
+def relative_pose(pixels: torch.Tensor, conf: Optional[torch.Tensor], cams: torch.Tensor, pairs: Sequence[Tuple[int, int]] = ((0, 1),),
+                  distortion: Optional[torch.Tensor] = None, threshold: float = 6.0, hypotheses: int = 1024, seed: int = 0,
+                  baseline: float = 1.0, refine: bool = False, huber: Optional[float] = None,
+                  return_hypotheses: bool = False) -> RelativePose:
+    """The relative pose of pairs of views from their detections and intrinsics alone: the step from pixels into locate_cameras, in
+    the presence of wrong detections.  pixels (B,V,J,2), conf (B,V,J) or None, cams (V,16) float64 and distortion (V,5) or None are
+    the arguments of locate_cameras, but of a record only fx fy cx cy and its lens row are read: the pose fields may be NaN.
+    pairs: up to 32 (a, b) of distinct view indices.  -> RelativePose(rotation, direction, cams, inliers, count, best, error,
+    status, refined, poses, scores, roots), one entry per pair; x_b = R x_a + t with |t| = 1.
+
+    Per pair, `hypotheses` (1 .. 65536) five-point problems are solved, each on five participating correspondences drawn with the
+    counter-based generator of synthesize_views under `seed`; each of its up to ten essential matrices gives a pose (the one that
+    puts the five samples in front of both cameras) and is scored over all participating correspondences by the Sampson distance in
+    pixels on the undistorted pixels: count = the correspondences within `threshold` (pixels, finite and > 0), cost = sum w
+    min(d^2, threshold^2), w = conf_a * conf_b.  A hypothesis keeps its best candidate; the winner has the most inliers, then the
+    lowest cost, then the lowest number (include/mpl_hip.h has the five steps).  A correspondence takes part when in both views
+    the weight is finite and > 0 and the pixel is finite and goes back through the lens.
+
+    Located (status 0): the winner has at least 6 inliers.  `cams` then holds a rig of the pair in the gauge of view a: record 0 is
+    view a with R = I at the origin, record 1 view b with R at -baseline * R^T t -- `baseline` (finite, > 0) is the length the
+    caller gives to what two views cannot see.  Invalid (3): fewer than 5 correspondences take part, no hypothesis is valid, the
+    winner has fewer than 6 inliers or the intrinsics are not finite; the poses are NaN, count 0, the inliers 0.  A winner is a
+    start, not a fit: from 136 correspondences with 2 px of noise and a quarter of each view's detections planted off it lies within
+    a few degrees; a detection moved along its epipolar line is an inlier of any two-view test, so a few planted ones remain.
+    refine=True adds one launch, the polish: refine_relative_pose(pixels, conf, cams, pairs, rotation, direction, distortion,
+    huber=huber, baseline=baseline, weight=inliers), whose pose becomes `rotation`, `direction` and `cams` and which is returned
+    whole as `refined`; inliers, count, best and error stay those of the hypothesis stage.  `huber` without `refine` raises.
+    return_hypotheses=True hands out every hypothesis: poses (P,H,12), NaN where void, scores (P,H,2), (0, inf) where void, and
+    roots (P,H), the real candidates.
+
+    The recipe from pixels and intrinsics to a rig: relative_pose(pairs=((0, 1),), refine=True) -> triangulate_pixels on views 0 and 1 under
+    .cams[0] -> locate_cameras(fixed=(0, 1), refine=True) with those two records in place -> bundle_adjust(fixed=(0, 1)).  Three
+    launches before the polish, no synchronisation, nothing read back, identical bits from run to run."""
+    from . import detrng
+    if huber is not None and not refine:
+        raise RuntimeError("huber is an option of the refinement: it needs refine=True")
+    h = _refine_options(huber, 20, 1e-8)[0]
+    try:
+        tau = float(threshold)
+    except (TypeError, ValueError):
+        tau = math.nan
+    if not (tau > 0.0 and math.isfinite(tau)):
+        raise RuntimeError("threshold must be a positive finite number of pixels (got %r)" % (threshold,))
+    try:
+        H = -1 if isinstance(hypotheses, bool) else operator.index(hypotheses)
+    except TypeError:
+        H = -1
+    if not 1 <= H <= 65536:
+        raise RuntimeError("hypotheses must be an integer in [1, 65536] (got %r)" % (hypotheses,))
+    try:
+        seed = -1 if isinstance(seed, bool) else operator.index(seed)
+    except TypeError:
+        raise RuntimeError("seed must be an integer (got %r)" % (seed,))
+    base = _baseline(baseline)
+    V = pixels.shape[1] if isinstance(pixels, torch.Tensor) and pixels.ndim == 4 else 0
+    flat = _pairs(pairs, V) if V else []                 # a pixels tensor of another form is _observations' to complain about
+    (pixels, conf), cams, distortion, B, V, J = _observations(None, pixels, conf, cams, distortion, with_points=False)
+    dev = pixels.device
+    P = len(flat) // 2
+    keys = (cabi.C.c_uint64 * P)(*(int(detrng._stream_key(seed, "relative_pose", lane=p)) for p in range(P)))
+    ws = torch.empty((cabi.load().mpl_relative_pose_workspace_bytes(B, P, J),), dtype=torch.uint8, device=dev)
+    f64 = dict(dtype=torch.float64, device=dev)
+    rotation, direction, out_cams = torch.empty((P, 3, 3), **f64), torch.empty((P, 3), **f64), torch.empty((P, 2, 16), **f64)
+    inliers = torch.empty((B, P, J), dtype=torch.float32, device=dev)
+    count = torch.empty((P,), dtype=torch.int32, device=dev)
+    best = torch.empty((P,), dtype=torch.int32, device=dev)
+    error = torch.empty((P,), **f64)
+    status = torch.empty((P,), dtype=torch.uint8, device=dev)
+    poses, scores = torch.empty((P, H, 12), **f64), torch.empty((P, H, 2), **f64)
+    roots = torch.empty((P, H), dtype=torch.int32, device=dev)
+    cabi.launch("relative_pose", dev, pixels.data_ptr(), ptr(conf), cams.data_ptr(), ptr(distortion), B, V, J, (cabi.C.c_int * len(flat))(*flat),
+                P, tau, H, keys, base, ws.data_ptr(), ws.numel(), rotation.data_ptr(), direction.data_ptr(), out_cams.data_ptr(),
+                inliers.data_ptr(), count.data_ptr(), best.data_ptr(), error.data_ptr(), status.data_ptr(), poses.data_ptr(),
+                scores.data_ptr(), roots.data_ptr())
+    refined = None
+    if refine:
+        refined = _refine_relative(pixels, conf, inliers, cams, flat, rotation, direction, distortion, h, 20, 1e-8, base)
+        rotation, direction, out_cams = refined.rotation, refined.direction, refined.cams
+    return RelativePose(rotation, direction, out_cams, inliers, count, best, error, status, refined, poses if return_hypotheses else None,
+                        scores if return_hypotheses else None, roots if return_hypotheses else None)
 
 
 def bundle_adjust(points: torch.Tensor, pixels: torch.Tensor, conf: Optional[torch.Tensor], cams: torch.Tensor,
