@@ -896,6 +896,51 @@ int mpl_refine_relative_pose(const float *pixels, const float *conf, const float
                              double *out_error, double *out_cost0, double *out_cost, int *out_used, int *out_iterations,
                              unsigned char *out_status, void *stream);
 
+/* ---- refinement of whole poses under bone-length constraints, csrc/refine_poses.hip.  mpl_refine_points moves every joint on its
+ * own; here the joints of a pose are one body on a tree with bones of known length.  Per pose, from the pose it is given,
+ *   E(X) = sum_{v,j} w_vj rho(|proj_v(X_j) - px_vj|^2) + bone_weight * sum_{live bones j} ((|X_j - X_p(j)| - L_j) / L_j)^2
+ * is minimised over the joints that take part.  The first sum is the cost of mpl_refine_points to the letter (arguments, layouts,
+ * limits, projection, lens, weights, view participation, rho and the IRLS weights), in px^2; the bone residual is relative, so
+ * bone_weight is px^2 per unit of relative length error whatever the world unit, and the bone term is always quadratic.  The
+ * reference has no such step (lib/multiviews/pictorial.py uses limb_length on a grid; mpl_rpsm is that search).
+ * limb: device float32, indexed by the child joint, the root's entry not read; limb_stride 0: one row (J,) for every pose, else
+ * (B,J) rows limb_stride >= joints apart.  parents: host, `joints` ints, -1 for the one root (as mpl_rpsm takes them).
+ * Participation: a bone is live when both its ends have a finite given point and a view that takes part, and L_j is finite and > 0
+ * (a NaN length switches a bone off).  A joint takes part when its given point is finite and it is seen by two views that take
+ * part, or by one and is an end of a live bone.  A joint that takes no part is returned bit for bit, its error is NaN and its views
+ * and bones count nowhere.
+ * Iteration: Levenberg-Marquardt on the 3 J' unknowns with the schedule and constants of mpl_refine_points.  H has one 3x3 block per
+ * joint (sum w' J^T J plus c u u^T of every live bone at the joint, u the unit vector child - parent, c = bone_weight / L^2) and
+ * the block -c u u^T per live bone; g likewise (a live bone with |d| = 0 contributes its residual and a zero gradient).
+ * (H + lambda diag H) delta = -g is solved on the tree, children eliminated before their parents, without fill-in, each 3x3 block
+ * by an unpivoted L D L^T (a pivot that is <= 0 or not finite gives a NaN step, which no trial survives).  A trial is accepted only
+ * if it lowers E strictly and leaves every joint that takes part at z_cam > 1e-9 in its views that take part: out_cost <= out_cost0.
+ * After a trial, accepted or not: converged when max |delta| <= step_tolerance * z_min, z_min the smallest such depth of the pose
+ * at the accepted pose; else capped when lambda > 1e12 or after max_iterations trials.  lambda, the trials and the status belong
+ * to the pose.
+ * Outputs: out_points (B,J,3); out_error (B,J) the plain weighted RMS of |r_v| in pixels per joint as in mpl_refine_points, NaN for
+ * a joint that takes no part; out_bone_error (B,J) = |d| - L in world units at the result, NaN at the root and at a bone that is
+ * not live; out_cost0, out_cost (B) = E at the given and the final pose in the mode of the call; out_iterations (B) the trials;
+ * out_status (B) bytes:
+ *   0 converged;  1 capped (a pose that stays underdetermined, such as one seen by a single camera, may end here);
+ *   2 passed through: max_iterations == 0 or no joint takes part; the points are returned bit for bit and everything is scored
+ *     (with no joint taking part the costs are 0 and every error is NaN);
+ *   3 invalid: a joint that takes part is at z_cam <= 1e-9 in a view that takes part at the given pose; every output of the pose
+ *     is NaN.  A statement about the pose: no device error, and no other pose is touched.
+ * conf, dist_dev, out_bone_error, out_cost0, out_cost, out_iterations and out_status may be NULL.
+ * One launch, one wave per pose, lane j owning joint j; fp64 on the fp32 tensors, every output rounded once, the children of a
+ * joint summed in index order, the sums over the pose reduced in a fixed order, no atomics: identical bits from run to run and
+ * from batching to batching.  The trial count is bounded by max_iterations whatever the data.  Stream-ordered, never synchronises;
+ * neither looks at nor sets the device error word.
+ * Refusals, in this order and before any device query: MPL_E_INVALID: limb or parents NULL; then those of mpl_refine_points;
+ * MPL_E_INVALID: a limb_stride that is neither 0 nor >= joints; MPL_E_UNSUPPORTED: a bone_weight that is negative or not finite;
+ * MPL_E_INVALID: parents that are not one tree (not exactly one -1, an entry that is no other joint, a cycle). */
+int mpl_refine_poses(const float *points, const float *pixels, const float *conf, const double *cams_dev, const double *dist_dev,
+                     const float *limb, long long limb_stride, const int *parents, int batch, int views, int joints, double huber,
+                     double bone_weight, int max_iterations, double step_tolerance, float *out_points, float *out_error,
+                     float *out_bone_error, double *out_cost0, double *out_cost, int *out_iterations, unsigned char *out_status,
+                     void *stream);
+
 /* ---- Procrustes alignment of predicted poses onto their targets, csrc/procrustes.hip: the transform behind PA-MPJPE (Protocol
  * 2), in place of lib/utils/pose_utils.py:61-143 PoseUtils.procrustes (a numpy port of MATLAB's procrustes, one 3x3 SVD per pose
  * on the host, which would force all_preds back to the host).  One launch aligns `batch` poses: target A and prediction B, both

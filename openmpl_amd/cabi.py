@@ -135,6 +135,8 @@ EXPORTS = ("mpl_hip_abi_version", "mpl_hip_error_string", "mpl_config_supported"
            "mpl_refine_points",
            # the transpose: Levenberg-Marquardt on the 6 pose unknowns of every camera, the points given; no counterpart either
            "mpl_refine_cameras",
+           # and the joints of a pose as one body: the same error plus bone-length terms, solved on the tree
+           "mpl_refine_poses",
            # and the step before it: a camera located from scratch by hypothesise-and-score over 6-point resections
            "mpl_locate_cameras_workspace_bytes", "mpl_locate_cameras",
            # and the step before that one: the relative pose of two views from their detections alone, by five-point hypotheses
@@ -331,6 +333,9 @@ def load():
         lib.mpl_refine_cameras.restype = C.c_int
         lib.mpl_refine_cameras.argtypes = [_fp, _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, C.c_uint,
                                            _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp]
+        lib.mpl_refine_poses.restype = C.c_int
+        lib.mpl_refine_poses.argtypes = [_fp, _fp, _fp, _fp, _fp, _fp, C.c_longlong, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int,
+                                         C.c_double, C.c_double, C.c_int, C.c_double, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp]
         lib.mpl_locate_cameras_workspace_bytes.restype = C.c_size_t
         lib.mpl_locate_cameras_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
         lib.mpl_locate_cameras.restype = C.c_int

@@ -956,6 +956,17 @@ int mpl_refine_cameras(const float* points, const float* pixels, const float* co
                                  (hipStream_t)stream);
 }
 
+int mpl_refine_poses(const float* points, const float* pixels, const float* conf, const double* cams_dev, const double* dist_dev,
+                     const float* limb, long long limb_stride, const int* parents, int batch, int views, int joints, double huber,
+                     double bone_weight, int max_iterations, double step_tolerance, float* out_points, float* out_error,
+                     float* out_bone_error, double* out_cost0, double* out_cost, int* out_iterations, unsigned char* out_status,
+                     void* stream) {
+    clear_stale_hip_error();
+    return launch_refine_poses(points, pixels, conf, cams_dev, dist_dev, limb, limb_stride, parents, batch, views, joints, huber,
+                               bone_weight, max_iterations, step_tolerance, out_points, out_error, out_bone_error, out_cost0, out_cost,
+                               out_iterations, out_status, (hipStream_t)stream);
+}
+
 size_t mpl_locate_cameras_workspace_bytes(int batch, int views, int joints) { return locate_cameras_workspace_bytes(batch, views, joints); }
 
 int mpl_locate_cameras(const float* points, const float* pixels, const float* conf, const double* cams_dev, const double* dist_dev,

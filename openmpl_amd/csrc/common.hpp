@@ -381,6 +381,14 @@ int launch_refine_cameras(const float* points, const float* pixels, const float*
                           double* out_cams, double* out_error, double* out_cost0, double* out_cost, int* out_used, int* out_iterations,
                           unsigned char* out_status, hipStream_t s);
 
+// refine_poses.hip: Levenberg-Marquardt refinement of whole poses on the same error plus bone-length terms on a tree, one wave per
+// pose (mpl_refine_poses); parents: host
+int launch_refine_poses(const float* points, const float* pixels, const float* conf, const double* cams_dev, const double* dist_dev,
+                        const float* limb, long long limb_stride, const int* parents, int B, int V, int J, double huber,
+                        double bone_weight, int max_iterations, double step_tolerance, float* out_points, float* out_error,
+                        float* out_bone_error, double* out_cost0, double* out_cost, int* out_iterations, unsigned char* out_status,
+                        hipStream_t s);
+
 // locate_cameras.hip: robust resection of every view from known 3D points, hypothesise-and-score (mpl_locate_cameras); keys: host,
 // one detrng stream key per view
 size_t locate_cameras_workspace_bytes(int B, int V, int J);

@@ -9,8 +9,9 @@ C ABI (mpl_triangulate_rays, mpl_epipolar_errors, csrc/geometry.hip) on the curr
 triangulate_rays_robust (mpl_triangulate_robust, a third kernel) puts the view selection of lib/multiviews/triangulate.py:88-112
 and a pair consensus in front of the same least-squares fit.  refine_points / reprojection_errors (mpl_refine_points,
 csrc/refine.hip) work in the detector's unit: Levenberg-Marquardt on the reprojection error of a point in pixels, and that error for
-any 3D estimate.  refine_cameras (mpl_refine_cameras, csrc/refine_cameras.hip) is its transpose -- the points given, the camera poses
-moved --, and bundle_adjust alternates the two.  locate_cameras (mpl_locate_cameras, csrc/locate_cameras.hip) is the step before
+any 3D estimate.  refine_poses (mpl_refine_poses, csrc/refine_poses.hip) refines the joints of a pose together, the same error plus
+bone-length terms on the tree of rpsm.  refine_cameras (mpl_refine_cameras, csrc/refine_cameras.hip) is the transpose of
+refine_points -- the points given, the camera poses moved --, and bundle_adjust alternates the two.  locate_cameras (mpl_locate_cameras, csrc/locate_cameras.hip) is the step before
 them: a camera located from no pose at all by hypothesise-and-score over 6-point resections.  relative_pose (mpl_relative_pose,
 csrc/relative_pose.hip) is the step before that one: the relative pose of two views from their detections and intrinsics alone, by
 hypothesise-and-score over five-point solutions.
@@ -244,6 +245,107 @@ def reprojection_errors(points: torch.Tensor, pixels: torch.Tensor, conf: Option
     predictions after de-normalisation."""
     r = _refine(points, pixels, conf, cams, distortion, 0.0, 0, 0.0)
     return r.errors, r.error
+
+
+class PosesRefined(NamedTuple):
+    """what refine_poses returns"""
+    points: torch.Tensor          # (B,J,3) float32
+    error: torch.Tensor           # (B,J) float32: the weighted root-mean-square reprojection error per joint, pixels
+    bone_error: torch.Tensor      # (B,J) float32: |X_j - X_parent(j)| - limb_length in world units; NaN at the root and dead bones
+    cost0: torch.Tensor           # (B,) float64: E at the given pose, in the mode of the call
+    cost: torch.Tensor            # (B,) float64: E at the final pose; never above cost0
+    iterations: torch.Tensor      # (B,) int32: trial steps made
+    status: torch.Tensor          # (B,) uint8: 0 converged, 1 capped, 2 passed through, 3 invalid
+
+
+def _parents(parents, J):
+    """`parents` as rpsm takes them -> a list of J ints that is one tree; the messages are those of rpsm"""
+    from . import rpsm as _rpsm
+    if parents is None:
+        if J != len(_rpsm.HUMAN_BODY_PARENTS):
+            raise ValueError("the default tree has %d joints, the points %d: pass parents" % (len(_rpsm.HUMAN_BODY_PARENTS), J))
+        parents = _rpsm.HUMAN_BODY_PARENTS
+    if isinstance(parents, torch.Tensor):
+        if parents.device.type != "cpu":
+            raise ValueError("parents is read on the host: pass a list or a CPU tensor")
+        parents = parents.tolist()
+    parents = [int(q) for q in parents]
+    if len(parents) != J:
+        raise ValueError("parents has %d entries, the points %d joints" % (len(parents), J))
+    _rpsm.tree_levels(parents)
+    return parents
+
+
+def bone_lengths(points: torch.Tensor, parents: Optional[Sequence[int]] = None) -> torch.Tensor:
+    """Plumbing, plain torch, no kernel: points (B,J,3) -> (B,J) float32, |X_j - X_parent(j)| and 0 at the root; NaN where an end is
+    NaN.  What feeds refine_poses' limb_length, for instance bone_lengths(p).nanmedian(0).values over the poses of a sequence.
+    parents: as refine_poses takes them (default: the 17-joint HumanBody tree)."""
+    if not isinstance(points, torch.Tensor) or points.ndim != 3 or points.shape[2] != 3:
+        raise RuntimeError("points: expected a tensor of shape (B,J,3), got %s"
+                           % (tuple(points.shape) if isinstance(points, torch.Tensor) else type(points).__name__,))
+    J = points.shape[1]
+    parents = _parents(parents, J)
+    idx = torch.tensor([q if q >= 0 else j for j, q in enumerate(parents)], dtype=torch.long, device=points.device)
+    return (points - points.index_select(1, idx)).to(torch.float32).norm(dim=-1)
+
+
+def refine_poses(points: torch.Tensor, pixels: torch.Tensor, conf: Optional[torch.Tensor], cams: torch.Tensor, limb_length: torch.Tensor,
+                 *, parents: Optional[Sequence[int]] = None, bone_weight: float = 1e4, distortion: Optional[torch.Tensor] = None,
+                 huber: Optional[float] = None, max_iterations: int = 50, step_tolerance: float = 1e-8) -> PosesRefined:
+    """Whole poses moved to the minimum of reprojection error plus bone-length error: the continuous counterpart of rpsm, and the
+    polish of any 3D estimate (triangulated, from rpsm, or the model's prediction) against the pixels.  Per pose,
+
+        E(X) = sum_{v,j} w_vj rho(|proj_v(X_j) - pixels_vj|^2) + bone_weight * sum_{bones j} ((|X_j - X_parent(j)| - L_j) / L_j)^2
+
+    by Levenberg-Marquardt over the joints of the pose at once, from the given pose.  points (B,J,3), pixels (B,V,J,2), conf (B,V,J) or
+    None, cams (V,16) float64, distortion (V,5) float64 or None, huber, max_iterations (0 .. 1000), step_tolerance: the arguments,
+    checks and limits of refine_points, and the first sum is its cost to the letter (px^2).  limb_length: float32 (J,) or (B,J) on
+    the device, indexed by the child joint; the root's entry is not read (bone_lengths makes one from poses).  parents: J ints, -1
+    for the one root, read on the host; default the 17-joint HumanBody tree of rpsm when J = 17, otherwise required; anything but
+    one tree is a ValueError before anything is launched.  bone_weight: finite, >= 0; the bone residual is relative, so the weight is
+    px^2 per unit of relative length error whatever the world unit, and the default 1e4 is (2 px / 2 %)^2.  The bone term is always
+    quadratic.  -> PosesRefined(points, error, bone_error, cost0, cost, iterations, status).
+
+    A bone is live when both its ends have a finite given point and a view that takes part, and its length is finite and > 0: a NaN
+    length switches a bone off.  A joint takes part when its given point is finite and it is seen by two views that take part, or by
+    one and is an end of a live bone -- which is what makes occluded joints and two-camera rigs usable.  A joint that takes no part
+    is returned bit for bit with error NaN.  A trial is accepted only if it lowers E and leaves every joint that takes part in front
+    of its cameras, so cost <= cost0.  Status per pose: converged (0) when the step is <= step_tolerance times the smallest depth of
+    the pose; capped (1); passed through (2): max_iterations == 0 or no joint takes part, points bit for bit, everything scored;
+    invalid (3): a joint that takes part is behind one of its cameras at the given pose, every output of the pose NaN.  error (B,J):
+    the plain weighted RMS of |r_v| per joint as in refine_points; bone_error (B,J): |d| - L at the result, NaN at the root and at
+    bones that are not live.  What stays underdetermined stays so and may end capped: a whole pose seen by one camera (its depth is
+    held by nothing but the lengths), a leaf seen by one view (one ray and one bone leave a near and a far solution; the start
+    decides).  One launch (one wave per pose), no synchronisation, identical bits from run to run and from batching to batching."""
+    h, max_iterations, tol = _refine_options(huber, max_iterations, step_tolerance)
+    try:
+        bw = float(bone_weight)
+    except (TypeError, ValueError):
+        bw = float("nan")
+    if not (bw >= 0.0 and math.isfinite(bw)):
+        raise RuntimeError("bone_weight must be a finite number >= 0 (got %r)" % (bone_weight,))
+    if isinstance(pixels, torch.Tensor) and pixels.ndim == 4 and min(pixels.shape[:3]) >= 1:
+        # a pixels tensor of another form is _observations' to complain about
+        B, J = pixels.shape[0], pixels.shape[2]
+        parents = _parents(parents, J)
+        if not isinstance(limb_length, torch.Tensor) or tuple(limb_length.shape) not in ((J,), (B, J)):
+            raise RuntimeError("limb_length: expected a tensor of shape %s or %s, got %s"
+                               % ((J,), (B, J), tuple(limb_length.shape) if isinstance(limb_length, torch.Tensor) else type(limb_length).__name__))
+        if limb_length.dtype != torch.float32:
+            raise RuntimeError("float32 tensors required (limb_length is %s)" % limb_length.dtype)
+    (points, pixels, conf), cams, distortion, B, V, J = _observations(points, pixels, conf, cams, distortion)
+    dev = pixels.device
+    if limb_length.device != dev:
+        raise RuntimeError("limb_length is on %s, pixels on %s" % (limb_length.device, dev))
+    limb_length = limb_length.contiguous()
+    out = PosesRefined(torch.empty((B, J, 3), dtype=torch.float32, device=dev), torch.empty((B, J), dtype=torch.float32, device=dev),
+                       torch.empty((B, J), dtype=torch.float32, device=dev), torch.empty((B,), dtype=torch.float64, device=dev),
+                       torch.empty((B,), dtype=torch.float64, device=dev), torch.empty((B,), dtype=torch.int32, device=dev),
+                       torch.empty((B,), dtype=torch.uint8, device=dev))
+    cabi.launch("refine_poses", dev, points.data_ptr(), pixels.data_ptr(), ptr(conf), cams.data_ptr(), ptr(distortion),
+                limb_length.data_ptr(), J if limb_length.ndim == 2 else 0, (cabi.C.c_int * J)(*parents), B, V, J, h, bw, max_iterations, tol,
+                *(t.data_ptr() for t in out))
+    return out
 
 
 class CamerasRefined(NamedTuple):
