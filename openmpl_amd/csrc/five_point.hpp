@@ -12,16 +12,11 @@
 // (x, y, z) on the ten cubics (polish).
 //
 // Storage: what is indexed by a loop counter (the 14 x 9 stacked system of the Jacobi, the 10 x 20 elimination, the Sturm chain)
-// goes through Strided<S>, element e at p[e * S] -- S = 64 on the device, where the FP_DOUBLES doubles of a lane are interleaved in LDS,
-// S = 1 in a host build.  Everything else has constant indices after unrolling and lives in registers.
+// goes through Strided<S> of hestenes.hpp -- S = 64 on the device, where the FP_DOUBLES doubles of a lane are interleaved in LDS,
+// S = 1 in a host build.  Everything else has constant indices after unrolling and lives in registers.  The rotation of the Jacobi
+// and the 3 x 3 factorisation of pose_of are those of hestenes.hpp.
 #pragma once
-#include <math.h>
-
-#if defined(__HIPCC__)
-#define MPL_FP_HD __host__ __device__ __forceinline__
-#else
-#define MPL_FP_HD inline
-#endif
+#include "hestenes.hpp"
 
 // the value as it is, but nothing the compiler knows about it
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -38,39 +33,32 @@ constexpr int FP_ROWS = 14;              // a column of the stacked [A; V]: 5 ro
 constexpr int FP_DOUBLES = 249;          // of a lane: the 10 x 20 cubics (the largest of the three uses), the ten roots and B(z) beside them
 constexpr int FP_SWEEPS = 30;            // a cap of the 9-column Jacobi
 constexpr double FP_ROT_EPS = 1e-15;     // columns with |a . b| <= this * |A|_F^2 are not turned
-constexpr int FP_SWEEPS3 = 6;            // the 3 x 3 factorisation: fixed, as in locate_cameras.hip
 constexpr int FP_MAX_ROOTS = 10, FP_ROOTS_AT = 200, FP_BZ_AT = 210;
 constexpr int FP_POLISH = 3;             // Gauss-Newton steps of a candidate on the ten cubics: fixed
 constexpr double FP_TRIM = 1e-13;        // a leading coefficient below this times the largest is no coefficient
 constexpr int FP_ISOLATE = 64, FP_BISECT = 80, FP_NEWTON = 3;
 constexpr double FP_DEPTH_MIN = 1e-9;    // CAMERA_Z_MIN of views.hpp: a sample at a depth <= this is not in front
 
-template <int S>
-struct Strided {
-    double* p;
-    MPL_FP_HD double& operator[](int e) const { return p[e * S]; }
-};
-
 // ---- polynomials in (x, y, z).  Degree 1: x y z 1.  Degree 2: x^2 xy xz y^2 yz z^2 x y z 1.  Degree 3, the columns of the
 // elimination: x^3 y^3 x^2y xy^2 x^2z x^2 y^2z y^2 xyz xy | x xz xz^2 y yz yz^2 1 z z^2 z^3
-MPL_FP_HD constexpr int exp1(int i, int v) { return i == v ? 1 : 0; }
-MPL_FP_HD constexpr int exp2(int i, int v) {
+MPL_HD constexpr int exp1(int i, int v) { return i == v ? 1 : 0; }
+MPL_HD constexpr int exp2(int i, int v) {
     return v == 0 ? (i == 0 ? 2 : (i == 1 || i == 2 || i == 6) ? 1 : 0)
          : v == 1 ? (i == 3 ? 2 : (i == 1 || i == 4 || i == 7) ? 1 : 0)
                   : (i == 5 ? 2 : (i == 2 || i == 4 || i == 8) ? 1 : 0);
 }
-MPL_FP_HD constexpr int slot2(int a, int b, int c) {
+MPL_HD constexpr int slot2(int a, int b, int c) {
     return a == 2 ? 0 : b == 2 ? 3 : c == 2 ? 5 : (a == 1 && b == 1) ? 1 : (a == 1 && c == 1) ? 2 : (b == 1 && c == 1) ? 4
          : a == 1 ? 6 : b == 1 ? 7 : c == 1 ? 8 : 9;
 }
-MPL_FP_HD constexpr int slot3(int a, int b, int c) {
+MPL_HD constexpr int slot3(int a, int b, int c) {
     return a == 3 ? 0 : b == 3 ? 1 : (a == 2 && b == 1) ? 2 : (a == 1 && b == 2) ? 3 : (a == 2 && c == 1) ? 4 : a == 2 ? 5
          : (b == 2 && c == 1) ? 6 : b == 2 ? 7 : (a == 1 && b == 1 && c == 1) ? 8 : (a == 1 && b == 1) ? 9
          : a == 1 ? 10 + c : b == 1 ? 13 + c : 16 + c;
 }
 
 // out2 += sign * a * b, a and b of degree 1
-MPL_FP_HD void mul11(const double (&a)[4], const double (&b)[4], double sign, double (&out)[10]) {
+MPL_HD void mul11(const double (&a)[4], const double (&b)[4], double sign, double (&out)[10]) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
 #pragma unroll
@@ -80,7 +68,7 @@ MPL_FP_HD void mul11(const double (&a)[4], const double (&b)[4], double sign, do
 }
 
 // out3 += sign * a * b, a of degree 2 and b of degree 1
-MPL_FP_HD void mul21(const double (&a)[10], const double (&b)[4], double sign, double (&out)[20]) {
+MPL_HD void mul21(const double (&a)[10], const double (&b)[4], double sign, double (&out)[20]) {
 #pragma unroll
     for (int i = 0; i < 10; ++i) {
 #pragma unroll
@@ -91,7 +79,7 @@ MPL_FP_HD void mul21(const double (&a)[10], const double (&b)[4], double sign, d
 
 // c += sign * a * b for polynomials in z, coefficients ascending
 template <int NA, int NB>
-MPL_FP_HD void mulz(const double (&a)[NA], const double (&b)[NB], double sign, double (&c)[NA + NB - 1]) {
+MPL_HD void mulz(const double (&a)[NA], const double (&b)[NB], double sign, double (&c)[NA + NB - 1]) {
 #pragma unroll
     for (int i = 0; i < NA; ++i) {
 #pragma unroll
@@ -103,7 +91,7 @@ MPL_FP_HD void mulz(const double (&a)[NA], const double (&b)[NB], double sign, d
 // same for all of them, and X, Y, Z, W are its columns at the four largest entries of its diagonal, in descending order (the lowest
 // index among equals), made orthonormal in that order.  The roots (x, y, z) then belong to the five samples and not to the way the null space was found, so that two
 // implementations meet the same near-coincident roots at the same hypotheses
-MPL_FP_HD void canonical_basis(double (&basis)[4][9]) {
+MPL_HD void canonical_basis(double (&basis)[4][9]) {
     double diag[9];
 #pragma unroll
     for (int e = 0; e < 9; ++e) diag[e] = basis[0][e] * basis[0][e] + basis[1][e] * basis[1][e] + basis[2][e] * basis[2][e] + basis[3][e] * basis[3][e];
@@ -160,7 +148,7 @@ MPL_FP_HD void canonical_basis(double (&basis)[4][9]) {
 // space in the rows of V below them, the lowest column among equals first; canonical_basis makes X, Y, Z, W of them.  basis[k][e]:
 // entry e of X, Y, Z, W
 template <int S>
-MPL_FP_HD void null_space(Strided<S> m, const double (&ya)[FP_SAMPLE][2], const double (&yb)[FP_SAMPLE][2], double (&basis)[4][9]) {
+MPL_HD void null_space(Strided<S> m, const double (&ya)[FP_SAMPLE][2], const double (&yb)[FP_SAMPLE][2], double (&basis)[4][9]) {
     double frob = 0.0;
 #pragma unroll
     for (int i = 0; i < FP_SAMPLE; ++i) {
@@ -197,9 +185,8 @@ MPL_FP_HD void null_space(Strided<S> m, const double (&ya)[FP_SAMPLE][2], const 
                 // measured against |A|_F^2 and not against |a| |b|: four columns shrink to nothing, and relative to themselves they
                 // would be turned against each other for ever
                 if (fabs(gamma) > FP_ROT_EPS * frob) {
-                    const double zeta = (beta - alpha) / (2.0 * gamma);
-                    const double t = copysign(1.0, zeta) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-                    const double cs = 1.0 / sqrt(1.0 + t * t), sn = cs * t;
+                    const Rotation rot = hestenes_rotation(alpha, beta, gamma);
+                    const double cs = rot.cs, sn = rot.sn;
 #pragma unroll
                     for (int r = 0; r < FP_ROWS; ++r) {
                         m[ca * FP_ROWS + r] = cs * a[r] - sn * b[r];
@@ -240,7 +227,7 @@ MPL_FP_HD void null_space(Strided<S> m, const double (&ya)[FP_SAMPLE][2], const 
 // ---- the ten cubics into the 10 x 20 matrix m (row-major, row r at m[20 r]): row 0 is det E, rows 1 .. 9 the entries of
 // (E E^T - tr(E E^T) / 2) E, row-major
 template <int S>
-MPL_FP_HD void constraints(Strided<S> m, const double (&basis)[4][9]) {
+MPL_HD void constraints(Strided<S> m, const double (&basis)[4][9]) {
     double E[9][4];                          // entry e of E as a polynomial of degree 1
 #pragma unroll
     for (int e = 0; e < 9; ++e) {
@@ -308,7 +295,7 @@ MPL_FP_HD void constraints(Strided<S> m, const double (&basis)[4][9]) {
 // ---- Gauss-Jordan elimination of the first ten columns with partial pivoting (the lowest row among equals) -> [I | B]; false:
 // a pivot that is zero or not a number
 template <int S>
-MPL_FP_HD bool eliminate(Strided<S> m) {
+MPL_HD bool eliminate(Strided<S> m) {
     for (int k = 0; k < 10; ++k) {
         int piv = k;
         double best = fabs(m[k * 20 + k]);
@@ -338,7 +325,7 @@ MPL_FP_HD bool eliminate(Strided<S> m) {
 // ---- B(z): row r holds the polynomials of x (4), y (4) and 1 (5), ascending, of <lead z> - z <lead>, for the rows 4 / 5 (x^2 z,
 // x^2), 6 / 7 (y^2 z, y^2) and 8 / 9 (xyz, xy) of the eliminated matrix
 template <int S>
-MPL_FP_HD void hidden_variable(Strided<S> m, double (&Bz)[3][13]) {
+MPL_HD void hidden_variable(Strided<S> m, double (&Bz)[3][13]) {
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
         const int e = (4 + 2 * r) * 20, f = (5 + 2 * r) * 20;
@@ -359,7 +346,7 @@ MPL_FP_HD void hidden_variable(Strided<S> m, double (&Bz)[3][13]) {
 }
 
 // det B(z), degree 10, ascending
-MPL_FP_HD void determinant(const double (&Bz)[3][13], double (&p)[11]) {
+MPL_HD void determinant(const double (&Bz)[3][13], double (&p)[11]) {
     double a[3][4], b[3][4], c[3][5];
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
@@ -393,14 +380,14 @@ MPL_FP_HD void determinant(const double (&Bz)[3][13], double (&p)[11]) {
 // polynomial k is at m[11 k ..], its degree at m[121 + k], root k at m[FP_ROOTS_AT + k] (a root is indexed by a loop counter too).
 // Every member is divided by its largest coefficient, a positive factor
 template <int S>
-MPL_FP_HD double horner(Strided<S> m, int at, int deg, double z) {
+MPL_HD double horner(Strided<S> m, int at, int deg, double z) {
     double v = m[at + deg];
     for (int k = deg - 1; k >= 0; --k) v = v * z + m[at + k];
     return v;
 }
 
 template <int S>
-MPL_FP_HD int trimmed_degree(Strided<S> m, int at, int deg, double& big) {
+MPL_HD int trimmed_degree(Strided<S> m, int at, int deg, double& big) {
     big = 0.0;
     for (int k = 0; k <= deg; ++k) big = fmax(big, fabs(m[at + k]));
     while (deg >= 0 && !(fabs(m[at + deg]) > FP_TRIM * big)) --deg;
@@ -408,7 +395,7 @@ MPL_FP_HD int trimmed_degree(Strided<S> m, int at, int deg, double& big) {
 }
 
 template <int S>
-MPL_FP_HD int sturm_changes(Strided<S> m, int members, double z) {
+MPL_HD int sturm_changes(Strided<S> m, int members, double z) {
     int changes = 0;
     double last = 0.0;
     for (int k = 0; k < members; ++k) {
@@ -422,7 +409,7 @@ MPL_FP_HD int sturm_changes(Strided<S> m, int members, double z) {
 }
 
 template <int S>
-MPL_FP_HD int real_roots(Strided<S> m, const double (&p)[11]) {
+MPL_HD int real_roots(Strided<S> m, const double (&p)[11]) {
 #pragma unroll
     for (int k = 0; k < 11; ++k) m[k] = p[k];
     double big;
@@ -499,7 +486,7 @@ MPL_FP_HD int real_roots(Strided<S> m, const double (&p)[11]) {
 
 // ---- (x, y) at a root z: the null vector of B(z), the cross product of the two rows that make the longest one (the lowest pair
 // among equals); false where its last entry is zero or the result is not finite
-MPL_FP_HD bool xy_at(const double (&Bz)[3][13], double z, double& x, double& y) {
+MPL_HD bool xy_at(const double (&Bz)[3][13], double z, double& x, double& y) {
     double v[3][3];
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
@@ -524,46 +511,15 @@ MPL_FP_HD bool xy_at(const double (&Bz)[3][13], double z, double& x, double& y) 
     return c[2] != 0.0 && fabs(x) <= 1.79769313486231570815e308 && fabs(y) <= 1.79769313486231570815e308;
 }
 
-// one Hestenes rotation of a 3 x 3: columns a and b of M (and of W) are turned so that a . b = 0 (as in locate_cameras.hip)
-MPL_FP_HD void rotate3(double (&M)[3][3], double (&W)[3][3], const int a, const int b) {
-    const double alpha = M[0][a] * M[0][a] + M[1][a] * M[1][a] + M[2][a] * M[2][a];
-    const double beta = M[0][b] * M[0][b] + M[1][b] * M[1][b] + M[2][b] * M[2][b];
-    const double gamma = M[0][a] * M[0][b] + M[1][a] * M[1][b] + M[2][a] * M[2][b];
-    double t = 0.0;
-    if (gamma != 0.0) {
-        const double zeta = (beta - alpha) / (2.0 * gamma);
-        t = copysign(1.0, zeta) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-    }
-    const double cs = 1.0 / sqrt(1.0 + t * t), sn = cs * t;
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        double x = M[r][a];
-        M[r][a] = cs * x - sn * M[r][b];
-        M[r][b] = sn * x + cs * M[r][b];
-        x = W[r][a];
-        W[r][a] = cs * x - sn * W[r][b];
-        W[r][b] = sn * x + cs * W[r][b];
-    }
-}
+MPL_HD double pick3(const double (&v)[3], int k) { return k == 0 ? v[0] : k == 1 ? v[1] : v[2]; }
 
-MPL_FP_HD double pick3(const double (&v)[3], int k) { return k == 0 ? v[0] : k == 1 ? v[1] : v[2]; }
-
-// ---- the pose of an essential matrix (row-major): E = U diag(s) V^T by the Jacobi above, u3 = u1 x u2 and V proper;
+// ---- the pose of an essential matrix (row-major): E = U diag(s) V^T by factor3 of hestenes.hpp, u3 = u1 x u2 and V proper;
 // R in {U W V^T, U W^T V^T}, t = +-u3 in the order (R1, +), (R1, -), (R2, +), (R2, -); the first combination under which the five
 // samples have positive depth in both cameras is kept.  pose: R row-major, then t.  false: none does, or E has no two singular values
-MPL_FP_HD bool pose_of(const double (&E)[9], const double (&ya)[FP_SAMPLE][2], const double (&yb)[FP_SAMPLE][2], double (&pose)[12]) {
+MPL_HD bool pose_of(const double (&E)[9], const double (&ya)[FP_SAMPLE][2], const double (&yb)[FP_SAMPLE][2], double (&pose)[12]) {
     double M[3][3] = {{E[0], E[1], E[2]}, {E[3], E[4], E[5]}, {E[6], E[7], E[8]}};
-    double W[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
-#pragma unroll
-    for (int sweep = 0; sweep < FP_SWEEPS3; ++sweep) {
-        rotate3(M, W, 0, 1);
-        rotate3(M, W, 0, 2);
-        rotate3(M, W, 1, 2);
-    }
-    double sv[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) sv[k] = sqrt(M[0][k] * M[0][k] + M[1][k] * M[1][k] + M[2][k] * M[2][k]);
-    const int last = (sv[2] <= sv[0] && sv[2] <= sv[1]) ? 2 : (sv[1] <= sv[0] ? 1 : 0);
+    double W[3][3], sv[3];
+    const int last = factor3(M, W, sv);
     const int i1 = (last + 1) % 3, i2 = (last + 2) % 3;          // (i1, i2, last) is an even permutation: V stays proper
     const double s1 = pick3(sv, i1), s2 = pick3(sv, i2);
     if (!(s1 > 0.0) || !(s2 > 0.0) || !(s1 <= 1.79769313486231570815e308) || !(s2 <= 1.79769313486231570815e308)) return false;
@@ -623,7 +579,7 @@ MPL_FP_HD bool pose_of(const double (&E)[9], const double (&ya)[FP_SAMPLE][2], c
 // nearly the same z, and (x, y) read off it are then only a start; the cubics tell the two apart.  A step that is not finite is
 // not taken
 template <int S>
-MPL_FP_HD void polish(Strided<S> m, double& x, double& y, double& z) {
+MPL_HD void polish(Strided<S> m, double& x, double& y, double& z) {
     for (int it = 0; it < FP_POLISH; ++it) {
         const double x2 = x * x, y2 = y * y, z2 = z * z;
         const double mono[20] = {x2 * x, y2 * y, x2 * y, x * y2, x2 * z, x2, y2 * z, y2, x * y * z, x * y,
@@ -661,7 +617,7 @@ MPL_FP_HD void polish(Strided<S> m, double& x, double& y, double& z) {
 // ---- the solver up to the roots: basis, B(z) and the roots of det B(z), left at m[FP_ROOTS_AT ..] -> their number (0 where the
 // elimination fails); m holds the ten cubics afterwards
 template <int S>
-MPL_FP_HD int solve(Strided<S> m, const double (&ya)[FP_SAMPLE][2], const double (&yb)[FP_SAMPLE][2], double (&basis)[4][9],
+MPL_HD int solve(Strided<S> m, const double (&ya)[FP_SAMPLE][2], const double (&yb)[FP_SAMPLE][2], double (&basis)[4][9],
                     double (&Bz)[3][13]) {
     null_space(m, ya, yb, basis);
     constraints(m, basis);
@@ -695,7 +651,7 @@ MPL_FP_HD int solve(Strided<S> m, const double (&ya)[FP_SAMPLE][2], const double
 
 // the essential matrix of the candidate at root z, (x, y, z) polished -> false where (x, y) cannot be formed
 template <int S>
-MPL_FP_HD bool essential_at(Strided<S> m, const double (&basis)[4][9], const double (&Bz)[3][13], double z, double (&E)[9]) {
+MPL_HD bool essential_at(Strided<S> m, const double (&basis)[4][9], const double (&Bz)[3][13], double z, double (&E)[9]) {
     double x, y;
     const bool ok = xy_at(Bz, z, x, y);
     polish(m, x, y, z);

@@ -19,27 +19,30 @@
 //      over the observations in their order, so the bits do not depend on how the hypotheses are dealt to workgroups.
 //   3. locate_select_kernel, one workgroup per view: the lexicographic winner (a total order, so any reduction tree gives the same
 //      one), the record, the inlier mask, the count and the error of the winner.
-// No atomics, nothing read back, no synchronisation.
+// No atomics, nothing read back, no synchronisation.  The scaffold of the three launches is consensus.hpp, shared with
+// relative_pose.hip; the rotation of the Jacobi, the 3 x 3 factorisation and the LDS addressing are hestenes.hpp.
 #include "common.hpp"
-#include "detrng.hpp"
+#include "consensus.hpp"
+#include "hestenes.hpp"
 #include "reprojection.hpp"
 
 namespace mpl {
 
 namespace {
 
-constexpr int LCAM_LANES = 64;           // hypotheses of one workgroup of the hypothesis kernel: one wave
-constexpr int LCAM_TILE = 64;            // observations staged in LDS at a time: one per lane
-constexpr int LCAM_SAMPLE = 6, LCAM_ATTEMPTS = 16, LCAM_MIN_INLIERS = 6;
+using consensus::LANES;
+using consensus::THREADS;
+using consensus::WAVES;
+
+constexpr int LCAM_SAMPLE = 6;
+constexpr int LCAM_REC = 6;              // a record, floats: X0 X1 X2 q0 q1 w; w = 0: takes no part
 constexpr int LCAM_ROWS = 24;            // a column of the stacked [A; V]: 12 rows of the system over 12 of the rotations
 constexpr int LCAM_SYSTEM = LCAM_ROWS * 12;
 constexpr int LCAM_SWEEPS = 30;          // a cap: the samples of the tests are orthogonal to LCAM_ROT_EPS after 6 to 9
 constexpr double LCAM_ROT_EPS = 1e-15;   // columns with |a . b| <= this * |a| |b| are not turned
-constexpr int LCAM_SWEEPS3 = 6;          // the 3 x 3 factorisation: fixed, as in procrustes.hip
-constexpr int LCAM_THREADS = 256, LCAM_WAVES = LCAM_THREADS / 64;
-constexpr int LCAM_LDS = LCAM_SYSTEM * LCAM_LANES * 8 + LCAM_TILE * 6 * 4;
+constexpr int LCAM_LDS = LCAM_SYSTEM * LANES * 8 + consensus::TILE * LCAM_REC * 4;
 
-// The workspace of a view, in doubles: a header | y (N,2) | the records (N,6) as floats: X0 X1 X2 q0 q1 w
+// The workspace of a view, in doubles: a header | y (N,2) | the records (N,LCAM_REC) as floats
 enum { LCAM_M = 0, LCAM_S = 3, LCAM_COUNT = 4, LCAM_USABLE = 5, LCAM_HDR = 8 };
 
 struct LocateParams {
@@ -68,73 +71,25 @@ __device__ __forceinline__ float* lcam_records(const LocateParams& p, unsigned v
     return reinterpret_cast<float*>(lcam_header(p, v) + LCAM_HDR + 2 * (size_t)p.N);
 }
 
-// |r|^2 of one observation under the record c, and whether the point is in front: the projection of refine_cameras.hip.  One
-// statement for the scoring loop and the winner's mask, so that both count the same observations
-__device__ __forceinline__ double lcam_residual2(const double (&c)[16], const Distortion d, float x0, float x1, float x2, float q0, float q1,
-                                                 bool& front) {
+// |r|^2 of the observation of record r under the camera record c, and whether the point is in front: the projection of
+// refine_cameras.hip.  One statement for the scoring loop and the winner's mask, so that both count the same observations
+__device__ __forceinline__ double lcam_residual2(const double (&c)[16], const Distortion d, const float* r, bool& front) {
     const Camera cam{c};
     double xc, yc, zc;
-    camera_coords(c, (double)x0, (double)x1, (double)x2, xc, yc, zc);
+    camera_coords(c, (double)r[0], (double)r[1], (double)r[2], xc, yc, zc);
     front = zc > CAMERA_Z_MIN;
     const Normalized yd = distort_normalized(xc / zc, yc / zc, d);
     const Pixel px = pixel_of(cam, yd.x, yd.y);
-    const double r0 = px.x - (double)q0, r1 = px.y - (double)q1;
+    const double r0 = px.x - (double)r[3], r1 = px.y - (double)r[4];
     return r0 * r0 + r1 * r1;
-}
-
-// the sums of a workgroup of LCAM_THREADS: down each wave by shuffles, then across the waves in their order; every thread gets them
-template <int K>
-__device__ __forceinline__ void lcam_block_sum(double (&a)[K], double (*sh_part)[4], double* sh_tot) {
-    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) a[k] += __shfl_down(a[k], off, 64);
-    }
-    __syncthreads();                                     // the last read of sh_tot is over
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) sh_part[wave][k] = a[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < K) {
-        double r = sh_part[0][threadIdx.x];
-        for (int w = 1; w < LCAM_WAVES; ++w) r += sh_part[w][threadIdx.x];
-        sh_tot[threadIdx.x] = r;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; ++k) a[k] = sh_tot[k];
-}
-
-// one Hestenes rotation of a 3 x 3: columns a and b of M (and of W) are turned so that a . b = 0
-__device__ __forceinline__ void lcam_rotate3(double (&M)[3][3], double (&W)[3][3], const int a, const int b) {
-    const double alpha = M[0][a] * M[0][a] + M[1][a] * M[1][a] + M[2][a] * M[2][a];
-    const double beta = M[0][b] * M[0][b] + M[1][b] * M[1][b] + M[2][b] * M[2][b];
-    const double gamma = M[0][a] * M[0][b] + M[1][a] * M[1][b] + M[2][a] * M[2][b];
-    double t = 0.0;
-    if (gamma != 0.0) {
-        const double zeta = (beta - alpha) / (2.0 * gamma);
-        t = copysign(1.0, zeta) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-    }
-    const double cs = 1.0 / sqrt(1.0 + t * t), sn = cs * t;
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        double x = M[r][a];
-        M[r][a] = cs * x - sn * M[r][b];
-        M[r][b] = sn * x + cs * M[r][b];
-        x = W[r][a];
-        W[r][a] = cs * x - sn * W[r][b];
-        W[r][b] = sn * x + cs * W[r][b];
-    }
 }
 
 }  // namespace
 
 // ---- 1. participation, normalised observations, records, centroid and scale
 template <bool LENS>
-__global__ __launch_bounds__(LCAM_THREADS) void locate_prepare_kernel(const LocateParams p) {
-    __shared__ double sh_cam[21], sh_part[LCAM_WAVES][4], sh_tot[4];
+__global__ __launch_bounds__(THREADS) void locate_prepare_kernel(const LocateParams p) {
+    __shared__ double sh_cam[21], sh_part[WAVES][4], sh_tot[4];
     const unsigned v = blockIdx.x, tid = threadIdx.x;
     if (tid < 16) sh_cam[tid] = p.cams[(size_t)v * 16 + tid];
     else if (LENS && tid < 21) sh_cam[tid] = p.dist[(size_t)v * 5 + (tid - 16)];
@@ -142,8 +97,7 @@ __global__ __launch_bounds__(LCAM_THREADS) void locate_prepare_kernel(const Loca
     double c[16];
 #pragma unroll
     for (int k = 0; k < 16; ++k) c[k] = sh_cam[k];
-    const Distortion d{LENS ? sh_cam[16] : 0.0, LENS ? sh_cam[17] : 0.0, LENS ? sh_cam[18] : 0.0, LENS ? sh_cam[19] : 0.0,
-                       LENS ? sh_cam[20] : 0.0};
+    const Distortion d = distortion_from<LENS>(sh_cam + 16);
     const Camera cam{c};
     bool finite = true;                                  // of the record, only the intrinsics are read
 #pragma unroll
@@ -152,7 +106,7 @@ __global__ __launch_bounds__(LCAM_THREADS) void locate_prepare_kernel(const Loca
     float* rec = lcam_records(p, v);
 
     double a[4] = {0.0, 0.0, 0.0, 0.0};                  // sum X, and the count
-    for (unsigned i = tid; i < p.N; i += LCAM_THREADS) {
+    for (unsigned i = tid; i < p.N; i += THREADS) {
         const unsigned b = i / p.J, j = i - b * p.J;
         const unsigned o = (b * p.V + v) * p.J + j;            // below 2^30, so twice it fits 32 bits
         const double w = p.conf ? (double)p.conf[o] : 1.0;
@@ -170,23 +124,23 @@ __global__ __launch_bounds__(LCAM_THREADS) void locate_prepare_kernel(const Loca
         }
         yv[2 * (size_t)i] = y0;
         yv[2 * (size_t)i + 1] = y1;
-        float* r = rec + 6 * (size_t)i;
+        float* r = rec + LCAM_REC * (size_t)i;
         r[0] = x0; r[1] = x1; r[2] = x2; r[3] = q0; r[4] = q1;
         r[5] = part ? (float)w : 0.0f;                   // a float32 confidence or 1: exact
         if (part) {
             a[0] += (double)x0; a[1] += (double)x1; a[2] += (double)x2; a[3] += 1.0;
         }
     }
-    lcam_block_sum(a, sh_part, sh_tot);
+    consensus::block_sum(a, sh_part, sh_tot);
     const double count = a[3], m0 = a[0] / count, m1 = a[1] / count, m2 = a[2] / count;
     double q[1] = {0.0};
-    for (unsigned i = tid; i < p.N; i += LCAM_THREADS) {       // the records this thread wrote itself
-        const float* r = rec + 6 * (size_t)i;
+    for (unsigned i = tid; i < p.N; i += THREADS) {       // the records this thread wrote itself
+        const float* r = rec + LCAM_REC * (size_t)i;
         if (!(r[5] > 0.0f)) continue;
         const double d0 = (double)r[0] - m0, d1 = (double)r[1] - m1, d2 = (double)r[2] - m2;
         q[0] += d0 * d0 + d1 * d1 + d2 * d2;
     }
-    lcam_block_sum(q, sh_part, sh_tot);
+    consensus::block_sum(q, sh_part, sh_tot);
     if (tid == 0) {
         double* hdr = lcam_header(p, v);
         hdr[LCAM_M] = m0; hdr[LCAM_M + 1] = m1; hdr[LCAM_M + 2] = m2;
@@ -199,82 +153,55 @@ __global__ __launch_bounds__(LCAM_THREADS) void locate_prepare_kernel(const Loca
 
 // ---- 2. one lane per hypothesis: sample, solve, score
 template <bool LENS>
-__global__ __launch_bounds__(LCAM_LANES) void locate_hypotheses_kernel(const LocateParams p) {
+__global__ __launch_bounds__(LANES) void locate_hypotheses_kernel(const LocateParams p) {
     extern __shared__ __attribute__((aligned(16))) double lcam_lds[];
-    double* sys = lcam_lds + threadIdx.x;                // element (row r, column c) of this lane at sys[(c * LCAM_ROWS + r) * 64]
-    float* tile = reinterpret_cast<float*>(lcam_lds + LCAM_SYSTEM * LCAM_LANES);
+    const Strided<LANES> sys{lcam_lds + threadIdx.x};    // element (row r, column c) of this lane at sys[c * LCAM_ROWS + r]
+    float* tile = reinterpret_cast<float*>(lcam_lds + LCAM_SYSTEM * LANES);
     __shared__ double sh_cam[21], sh_hdr[LCAM_HDR];
-    const unsigned lane = threadIdx.x, v = blockIdx.y, h = blockIdx.x * LCAM_LANES + lane;
+    const unsigned lane = threadIdx.x, v = blockIdx.y, h = blockIdx.x * LANES + lane;
     if (lane < 16) sh_cam[lane] = p.cams[(size_t)v * 16 + lane];
     else if (LENS && lane < 21) sh_cam[lane] = p.dist[(size_t)v * 5 + (lane - 16)];
     else if (lane >= 32 && lane < 32 + LCAM_HDR) sh_hdr[lane - 32] = lcam_header(p, v)[lane - 32];
     __syncthreads();
-    const bool live = h < p.H;
-    const double nan = __builtin_nan("");
-    double* pose_out = p.poses + ((size_t)v * p.H + h) * 12;
-    double* score_out = p.scores + ((size_t)v * p.H + h) * 2;
+    const consensus::Hypothesis hyp = consensus::hypothesis_at(p.poses, p.scores, v, p.H, h);
     // a view that is passed through, or that has no six observations: every hypothesis is void (the same for the whole workgroup)
     if ((p.fixed_mask >> v & 1u) || sh_hdr[LCAM_USABLE] == 0.0) {
-        if (live) {
-            for (int k = 0; k < 12; ++k) pose_out[k] = nan;
-            score_out[0] = 0.0;
-            score_out[1] = __builtin_inf();
-        }
+        hyp.write_void();
         return;
     }
     double c[16];
 #pragma unroll
     for (int k = 0; k < 4; ++k) c[k] = sh_cam[k];
-    const Distortion d{LENS ? sh_cam[16] : 0.0, LENS ? sh_cam[17] : 0.0, LENS ? sh_cam[18] : 0.0, LENS ? sh_cam[19] : 0.0,
-                       LENS ? sh_cam[20] : 0.0};
+    const Distortion d = distortion_from<LENS>(sh_cam + 16);
     const double m0 = sh_hdr[LCAM_M], m1 = sh_hdr[LCAM_M + 1], m2 = sh_hdr[LCAM_M + 2], s = sh_hdr[LCAM_S];
     const double* yv = lcam_y(p, v);
     const float* rec = lcam_records(p, v);
 
-    // six distinct participating slots; a lane beyond H draws like any other (every slot is below N) and writes nothing
-    bool ok = true;
     unsigned pick[LCAM_SAMPLE];
-    const unsigned long long key = p.keys[v];
-#pragma unroll
-    for (int k = 0; k < LCAM_SAMPLE; ++k) {
-        bool got = false;
-        unsigned nk = 0;
-        for (int a = 0; a < LCAM_ATTEMPTS; ++a) {
-            const unsigned n = (unsigned)(detrng_draw(key, ((unsigned long long)h * LCAM_SAMPLE + k) * LCAM_ATTEMPTS + a) * (double)p.N);
-            bool good = !got && rec[6 * (size_t)n + 5] > 0.0f;
-#pragma unroll
-            for (int i = 0; i < k; ++i) good = good && n != pick[i];
-            if (good) {
-                got = true;
-                nk = n;
-            }
-        }
-        pick[k] = nk;
-        ok = ok && got;
-    }
+    bool ok = consensus::draw_distinct(p.keys[v], h, p.N, [rec](unsigned n) { return rec[LCAM_REC * (size_t)n + 5] > 0.0f; }, pick);
 
     // the system [Xh, 0, -y0 Xh; 0, Xh, -y1 Xh] on Xh = (s (X - m), 1), over the identity that collects the rotations
     double X[LCAM_SAMPLE][3];                            // the sample points as given: the depth test at the end reads them
     double xh[LCAM_SAMPLE][3];
 #pragma unroll
     for (int i = 0; i < LCAM_SAMPLE; ++i) {
-        const float* r = rec + 6 * (size_t)pick[i];
+        const float* r = rec + LCAM_REC * (size_t)pick[i];
         X[i][0] = (double)r[0]; X[i][1] = (double)r[1]; X[i][2] = (double)r[2];
         xh[i][0] = s * (X[i][0] - m0); xh[i][1] = s * (X[i][1] - m1); xh[i][2] = s * (X[i][2] - m2);
         const double y0 = yv[2 * (size_t)pick[i]], y1 = yv[2 * (size_t)pick[i] + 1];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const double e = k < 3 ? xh[i][k] : 1.0;
-            sys[((k + 0) * LCAM_ROWS + 2 * i) * 64] = e;
-            sys[((k + 4) * LCAM_ROWS + 2 * i) * 64] = 0.0;
-            sys[((k + 8) * LCAM_ROWS + 2 * i) * 64] = -y0 * e;
-            sys[((k + 0) * LCAM_ROWS + 2 * i + 1) * 64] = 0.0;
-            sys[((k + 4) * LCAM_ROWS + 2 * i + 1) * 64] = e;
-            sys[((k + 8) * LCAM_ROWS + 2 * i + 1) * 64] = -y1 * e;
+            sys[(k + 0) * LCAM_ROWS + 2 * i] = e;
+            sys[(k + 4) * LCAM_ROWS + 2 * i] = 0.0;
+            sys[(k + 8) * LCAM_ROWS + 2 * i] = -y0 * e;
+            sys[(k + 0) * LCAM_ROWS + 2 * i + 1] = 0.0;
+            sys[(k + 4) * LCAM_ROWS + 2 * i + 1] = e;
+            sys[(k + 8) * LCAM_ROWS + 2 * i + 1] = -y1 * e;
         }
     }
     for (int col = 0; col < 12; ++col)
-        for (int r = 0; r < 12; ++r) sys[(col * LCAM_ROWS + 12 + r) * 64] = r == col ? 1.0 : 0.0;
+        for (int r = 0; r < 12; ++r) sys[col * LCAM_ROWS + 12 + r] = r == col ? 1.0 : 0.0;
 
     // one-sided Jacobi: rotations from the right make the columns of A orthogonal, A V = U S; cyclic sweeps until no lane of the
     // wave turns a pair (a value that is not a number turns none)
@@ -285,13 +212,11 @@ __global__ __launch_bounds__(LCAM_LANES) void locate_hypotheses_kernel(const Loc
         for (int ca = 0; ca < 11; ++ca) {
 #pragma unroll 1
             for (int cb = ca + 1; cb < 12; ++cb) {
-                double* pa = sys + ca * LCAM_ROWS * 64;
-                double* pb = sys + cb * LCAM_ROWS * 64;
                 double a[LCAM_ROWS], b[LCAM_ROWS];
 #pragma unroll
                 for (int r = 0; r < LCAM_ROWS; ++r) {
-                    a[r] = pa[r * 64];
-                    b[r] = pb[r * 64];
+                    a[r] = sys[ca * LCAM_ROWS + r];
+                    b[r] = sys[cb * LCAM_ROWS + r];
                 }
                 double alpha = 0.0, beta = 0.0, gamma = 0.0;
 #pragma unroll
@@ -301,13 +226,12 @@ __global__ __launch_bounds__(LCAM_LANES) void locate_hypotheses_kernel(const Loc
                     gamma += a[r] * b[r];
                 }
                 if (fabs(gamma) > LCAM_ROT_EPS * sqrt(alpha * beta)) {
-                    const double zeta = (beta - alpha) / (2.0 * gamma);
-                    const double t = copysign(1.0, zeta) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-                    const double cs = 1.0 / sqrt(1.0 + t * t), sn = cs * t;
+                    const Rotation rot = hestenes_rotation<true>(alpha, beta, gamma);
+                    const double cs = rot.cs, sn = rot.sn;
 #pragma unroll
                     for (int r = 0; r < LCAM_ROWS; ++r) {
-                        pa[r * 64] = cs * a[r] - sn * b[r];
-                        pb[r * 64] = sn * a[r] + cs * b[r];
+                        sys[ca * LCAM_ROWS + r] = cs * a[r] - sn * b[r];
+                        sys[cb * LCAM_ROWS + r] = sn * a[r] + cs * b[r];
                     }
                     turned = true;
                 }
@@ -322,7 +246,7 @@ __global__ __launch_bounds__(LCAM_LANES) void locate_hypotheses_kernel(const Loc
         double n2 = 0.0;
 #pragma unroll
         for (int r = 0; r < 12; ++r) {
-            const double e = sys[(col * LCAM_ROWS + r) * 64];
+            const double e = sys[col * LCAM_ROWS + r];
             n2 += e * e;
         }
         if (n2 < smin) {
@@ -332,7 +256,7 @@ __global__ __launch_bounds__(LCAM_LANES) void locate_hypotheses_kernel(const Loc
     }
     double P[12];
 #pragma unroll
-    for (int r = 0; r < 12; ++r) P[r] = sys[(kmin * LCAM_ROWS + 12 + r) * 64];
+    for (int r = 0; r < 12; ++r) P[r] = sys[kmin * LCAM_ROWS + 12 + r];
     // the sign that puts the six sample points in front, summed
     double depth = 0.0;
 #pragma unroll
@@ -343,19 +267,10 @@ __global__ __launch_bounds__(LCAM_LANES) void locate_hypotheses_kernel(const Loc
     }
     // M = U S W^T by the same Jacobi on 3 x 3: R = U W^T, the shortest column turned over where det M < 0
     double M[3][3] = {{P[0], P[1], P[2]}, {P[4], P[5], P[6]}, {P[8], P[9], P[10]}};
-    double W[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
+    double W[3][3], sv[3], sg[3];
     const double det = M[0][0] * (M[1][1] * M[2][2] - M[1][2] * M[2][1]) - M[0][1] * (M[1][0] * M[2][2] - M[1][2] * M[2][0]) +
                        M[0][2] * (M[1][0] * M[2][1] - M[1][1] * M[2][0]);
-#pragma unroll
-    for (int sweep = 0; sweep < LCAM_SWEEPS3; ++sweep) {
-        lcam_rotate3(M, W, 0, 1);
-        lcam_rotate3(M, W, 0, 2);
-        lcam_rotate3(M, W, 1, 2);
-    }
-    double sv[3], sg[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) sv[k] = sqrt(M[0][k] * M[0][k] + M[1][k] * M[1][k] + M[2][k] * M[2][k]);
-    const int last = (sv[2] <= sv[0] && sv[2] <= sv[1]) ? 2 : (sv[1] <= sv[0] ? 1 : 0);
+    const int last = factor3(M, W, sv);
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         ok = ok && sv[k] > 0.0;
@@ -380,108 +295,49 @@ __global__ __launch_bounds__(LCAM_LANES) void locate_hypotheses_kernel(const Loc
         camera_coords(c, X[i][0], X[i][1], X[i][2], xc, yc, zc);
         ok = ok && zc > CAMERA_Z_MIN;
     }
-    if (live) {
+    if (hyp.live) {
 #pragma unroll
-        for (int k = 0; k < 12; ++k) pose_out[k] = ok ? c[4 + k] : nan;
+        for (int k = 0; k < 12; ++k) hyp.pose[k] = ok ? c[4 + k] : __builtin_nan("");
     }
 
     // the score over all observations in their order; a void lane goes along and is overwritten at the end
-    double cost = 0.0;
-    int count = 0;
-    for (unsigned base = 0; base < p.N; base += LCAM_TILE) {
-        __syncthreads();                                 // the tile before is read
-        if (base + lane < p.N) {
-            const float2* g = reinterpret_cast<const float2*>(rec + 6 * (size_t)(base + lane));
-            float2* t = reinterpret_cast<float2*>(tile + 6 * lane);
-            t[0] = g[0]; t[1] = g[1]; t[2] = g[2];
-        }
-        __syncthreads();
-        const unsigned n = min((unsigned)LCAM_TILE, p.N - base);
-        for (unsigned i = 0; i < n; ++i) {
-            const float* r = tile + 6 * i;               // the same address in every lane
-            const float w = r[5];
-            if (!(w > 0.0f)) continue;
-            bool front;
-            const double r2 = lcam_residual2(c, d, r[0], r[1], r[2], r[3], r[4], front);
-            const bool in = front && r2 <= p.tau2;
-            count += in ? 1 : 0;
-            cost += (double)w * (in ? r2 : p.tau2);
-        }
-    }
-    if (live) {
-        score_out[0] = ok ? (double)count : 0.0;
-        score_out[1] = ok ? cost : __builtin_inf();
-    }
+    const consensus::Score sc = consensus::score_tiled<float, LCAM_REC, float2>(
+        rec, p.N, tile, p.tau2, [&c, d](const float* r, bool& front) { return lcam_residual2(c, d, r, front); });
+    hyp.write_score(ok, sc.count, sc.cost);
 }
 
 // ---- 3. the winner of a view, its record, mask, count and error
 template <bool LENS>
-__global__ __launch_bounds__(LCAM_THREADS) void locate_select_kernel(const LocateParams p) {
-    __shared__ double sh_cam[21], sh_part[LCAM_WAVES][4], sh_tot[4], sh_usable;
-    __shared__ double sh_cnt[LCAM_WAVES], sh_cost[LCAM_WAVES];
-    __shared__ int sh_h[LCAM_WAVES];
-    const unsigned v = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+__global__ __launch_bounds__(THREADS) void locate_select_kernel(const LocateParams p) {
+    __shared__ double sh_cam[21], sh_part[WAVES][4], sh_tot[4], sh_usable;
+    const unsigned v = blockIdx.x, tid = threadIdx.x;
     // the given record, read before its row of out_cams is written (out_cams may be cams)
     if (tid < 16) sh_cam[tid] = p.cams[(size_t)v * 16 + tid];
     else if (LENS && tid < 21) sh_cam[tid] = p.dist[(size_t)v * 5 + (tid - 16)];
     else if (tid == 32) sh_usable = lcam_header(p, v)[LCAM_USABLE];
     __syncthreads();
     const bool fixed = p.fixed_mask >> v & 1u;
-
-    // most inliers, then the lowest cost, then the lowest number, among the hypotheses that are not void
-    double bc = -1.0, be = __builtin_inf();
-    int bh = -1;
-    if (!fixed && sh_usable != 0.0) {
-        const double* sc = p.scores + (size_t)v * p.H * 2;
-        for (unsigned h = tid; h < p.H; h += LCAM_THREADS) {
-            const double cn = sc[2 * (size_t)h], e = sc[2 * (size_t)h + 1];
-            if (!(e <= FINITE_MAX)) continue;
-            if (bh < 0 || cn > bc || (cn == bc && e < be)) {
-                bc = cn; be = e; bh = (int)h;
-            }
-        }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const double oc = __shfl_down(bc, off, 64), oe = __shfl_down(be, off, 64);
-        const int oh = __shfl_down(bh, off, 64);
-        if (oh >= 0 && (bh < 0 || oc > bc || (oc == bc && (oe < be || (oe == be && oh < bh))))) {
-            bc = oc; be = oe; bh = oh;
-        }
-    }
-    if (lane == 0) {
-        sh_cnt[wave] = bc; sh_cost[wave] = be; sh_h[wave] = bh;
-    }
-    __syncthreads();
-    bc = sh_cnt[0]; be = sh_cost[0]; bh = sh_h[0];
-    for (int w = 1; w < LCAM_WAVES; ++w) {
-        const double oc = sh_cnt[w], oe = sh_cost[w];
-        const int oh = sh_h[w];
-        if (oh >= 0 && (bh < 0 || oc > bc || (oc == bc && (oe < be || (oe == be && oh < bh))))) {
-            bc = oc; be = oe; bh = oh;
-        }
-    }
-    const bool located = bh >= 0 && bc >= (double)LCAM_MIN_INLIERS;
+    const consensus::Winner best = consensus::select_winner(p.scores, v, p.H, !fixed && sh_usable != 0.0);
+    const bool located = best.located();
 
     // the record that is scored: the winner's pose, or the given one of a view that is passed through
     double c[16];
 #pragma unroll
     for (int k = 0; k < 4; ++k) c[k] = sh_cam[k];
 #pragma unroll
-    for (int k = 0; k < 12; ++k) c[4 + k] = located ? p.poses[((size_t)v * p.H + (unsigned)bh) * 12 + k] : sh_cam[4 + k];
-    const Distortion d{LENS ? sh_cam[16] : 0.0, LENS ? sh_cam[17] : 0.0, LENS ? sh_cam[18] : 0.0, LENS ? sh_cam[19] : 0.0,
-                       LENS ? sh_cam[20] : 0.0};
+    for (int k = 0; k < 12; ++k) c[4 + k] = located ? p.poses[((size_t)v * p.H + (unsigned)best.h) * 12 + k] : sh_cam[4 + k];
+    const Distortion d = distortion_from<LENS>(sh_cam + 16);
     const float* rec = lcam_records(p, v);
     const bool scored = located || fixed;
     double a[2] = {0.0, 0.0};                            // sum |r|^2 over the inliers, and their count
-    for (unsigned i = tid; i < p.N; i += LCAM_THREADS) {
+    for (unsigned i = tid; i < p.N; i += THREADS) {
         const unsigned b = i / p.J, j = i - b * p.J;
         const unsigned o = (b * p.V + v) * p.J + j;
-        const float* r = rec + 6 * (size_t)i;
+        const float* r = rec + LCAM_REC * (size_t)i;
         bool in = false;
         if (scored && r[5] > 0.0f) {
             bool front;
-            const double r2 = lcam_residual2(c, d, r[0], r[1], r[2], r[3], r[4], front);
+            const double r2 = lcam_residual2(c, d, r, front);
             in = front && r2 <= p.tau2;
             if (in) {
                 a[0] += r2;
@@ -490,20 +346,20 @@ __global__ __launch_bounds__(LCAM_THREADS) void locate_select_kernel(const Locat
         }
         p.out_inliers[o] = in ? 1.0f : 0.0f;
     }
-    lcam_block_sum(a, sh_part, sh_tot);
+    consensus::block_sum(a, sh_part, sh_tot);
     if (tid == 0) {
         double* row = p.out_cams + (size_t)v * 16;
 #pragma unroll
         for (int k = 0; k < 16; ++k) row[k] = c[k];      // the given bits where nothing was located
         p.out_count[v] = (int)a[1];
-        p.out_best[v] = fixed ? -1 : bh;
+        p.out_best[v] = fixed ? -1 : best.h;
         p.out_error[v] = a[1] > 0.0 ? sqrt(a[0] / a[1]) : __builtin_nan("");
         p.out_status[v] = (unsigned char)(fixed ? LM_PASSED_THROUGH : located ? LM_CONVERGED : LM_INVALID);
     }
 }
 
 size_t locate_cameras_workspace_bytes(int B, int V, int J) {
-    if (B <= 0 || V <= 0 || J <= 0 || V > MPL_MAX_VIEWS || J > 64 || (long long)B * V * J > (1ll << 30)) return 0;
+    if (!consensus::sizes_ok(B, V, J)) return 0;
     return (size_t)V * (LCAM_HDR + 5 * (size_t)B * (size_t)J) * sizeof(double);
 }
 
@@ -513,8 +369,7 @@ int launch_locate_cameras(const float* points, const float* pixels, const float*
                           double* out_error, unsigned char* out_status, double* out_poses, double* out_scores, hipStream_t s) {
     if (const int e = refine_args_check(points, pixels, cams_dev, out_cams, out_error, B, V, J, 0, 0.0)) return e;
     if (!keys || !out_inliers || !out_count || !out_best || !out_status || !out_poses || !out_scores) return MPL_E_INVALID;
-    if (!(threshold > 0.0) || !(threshold <= FINITE_MAX) || !(threshold * threshold <= FINITE_MAX) || hypotheses < 1 || hypotheses > 65536)
-        return MPL_E_UNSUPPORTED;
+    if (const int e = consensus::options_check(threshold, hypotheses)) return e;
     if (!workspace || workspace_bytes < locate_cameras_workspace_bytes(B, V, J)) return MPL_E_WORKSPACE;
     LocateParams p;
     p.points = points; p.px = pixels; p.conf = conf; p.cams = cams_dev; p.dist = dist_dev;
@@ -524,26 +379,9 @@ int launch_locate_cameras(const float* points, const float* pixels, const float*
     p.tau2 = threshold * threshold;
     p.N = (unsigned)(B * J); p.V = (unsigned)V; p.J = (unsigned)J; p.H = (unsigned)hypotheses; p.fixed_mask = fixed_mask;
     for (int v = 0; v < MPL_MAX_VIEWS; ++v) p.keys[v] = v < V ? keys[v] : 0ull;
-    if (const int e = dist_dev ? kernel_lds_once<locate_hypotheses_kernel<true>>(LCAM_LDS, LCAM_LANES)
-                               : kernel_lds_once<locate_hypotheses_kernel<false>>(LCAM_LDS, LCAM_LANES))
-        return e;
-    const dim3 views((unsigned)V), hyp((p.H + LCAM_LANES - 1) / LCAM_LANES, (unsigned)V);
-    {
-        ProfScope prof(MPL_K_FUSE_HEAD, s);
-        if (dist_dev) hipLaunchKernelGGL(locate_prepare_kernel<true>, views, dim3(LCAM_THREADS), 0, s, p);
-        else hipLaunchKernelGGL(locate_prepare_kernel<false>, views, dim3(LCAM_THREADS), 0, s, p);
-    }
-    {
-        ProfScope prof(MPL_K_FUSE_HEAD, s);
-        if (dist_dev) hipLaunchKernelGGL(locate_hypotheses_kernel<true>, hyp, dim3(LCAM_LANES), LCAM_LDS, s, p);
-        else hipLaunchKernelGGL(locate_hypotheses_kernel<false>, hyp, dim3(LCAM_LANES), LCAM_LDS, s, p);
-    }
-    {
-        ProfScope prof(MPL_K_FUSE_HEAD, s);
-        if (dist_dev) hipLaunchKernelGGL(locate_select_kernel<true>, views, dim3(LCAM_THREADS), 0, s, p);
-        else hipLaunchKernelGGL(locate_select_kernel<false>, views, dim3(LCAM_THREADS), 0, s, p);
-    }
-    return hip_check_launch();
+    return consensus::launch<locate_prepare_kernel<true>, locate_prepare_kernel<false>, locate_hypotheses_kernel<true>,
+                             locate_hypotheses_kernel<false>, locate_select_kernel<true>, locate_select_kernel<false>>(
+        dist_dev != nullptr, p.V, p.H, LCAM_LDS, p, s);
 }
 
 }  // namespace mpl

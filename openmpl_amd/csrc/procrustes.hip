@@ -12,6 +12,7 @@
 // M^T M keeps the small singular values to their own relative accuracy.  A fixed number of sweeps, unrolled, on named registers:
 // no local array is indexed dynamically, so nothing lives in scratch.
 #include "common.hpp"
+#include "hestenes.hpp"
 
 namespace mpl {
 
@@ -45,12 +46,8 @@ __device__ __forceinline__ bool proc_takes_part(const ProcArgs& p, size_t b, int
 __device__ __forceinline__ void proc_rotate(double& a0, double& a1, double& a2, double& b0, double& b1, double& b2, double& va0,
                                             double& va1, double& va2, double& vb0, double& vb1, double& vb2) {
     const double alpha = a0 * a0 + a1 * a1 + a2 * a2, beta = b0 * b0 + b1 * b1 + b2 * b2, gamma = a0 * b0 + a1 * b1 + a2 * b2;
-    double t = 0.0;
-    if (gamma != 0.0) {
-        const double zeta = (beta - alpha) / (2.0 * gamma);
-        t = copysign(1.0, zeta) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));       // |zeta| = inf: t = 0
-    }
-    const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
+    const Rotation rot = hestenes_rotation(alpha, beta, gamma);
+    const double c = rot.cs, s = rot.sn;
     double x;
     x = a0; a0 = c * x - s * b0; b0 = s * x + c * b0;
     x = a1; a1 = c * x - s * b1; b1 = s * x + c * b1;

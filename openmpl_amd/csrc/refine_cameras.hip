@@ -208,8 +208,7 @@ __global__ __launch_bounds__(RCAM_THREADS) void refine_cameras_kernel(const Refi
         double c[16];
 #pragma unroll
         for (int k = 0; k < 16; ++k) c[k] = sh_cam[k];
-        const Distortion d{LENS ? sh_cam[16] : 0.0, LENS ? sh_cam[17] : 0.0, LENS ? sh_cam[18] : 0.0, LENS ? sh_cam[19] : 0.0,
-                           LENS ? sh_cam[20] : 0.0};
+        const Distortion d = distortion_from<LENS>(sh_cam + 16);
         double acc[RCAM_USED], zmin = __builtin_inf();
 #pragma unroll
         for (int k = 0; k < RCAM_USED; ++k) acc[k] = 0.0;

@@ -183,10 +183,7 @@ __global__ __launch_bounds__(RREL_THREADS) void refine_relative_kernel(const Ref
         ca[k] = sh_cam[0][k];
         cb[k] = sh_cam[1][k];
     }
-    const Distortion da{LENS ? sh_cam[0][16] : 0.0, LENS ? sh_cam[0][17] : 0.0, LENS ? sh_cam[0][18] : 0.0, LENS ? sh_cam[0][19] : 0.0,
-                        LENS ? sh_cam[0][20] : 0.0};
-    const Distortion db{LENS ? sh_cam[1][16] : 0.0, LENS ? sh_cam[1][17] : 0.0, LENS ? sh_cam[1][18] : 0.0, LENS ? sh_cam[1][19] : 0.0,
-                        LENS ? sh_cam[1][20] : 0.0};
+    const Distortion da = distortion_from<LENS>(sh_cam[0] + 16), db = distortion_from<LENS>(sh_cam[1] + 16);
     bool finite = true;
 #pragma unroll
     for (int k = 0; k < 4; ++k) finite = finite && fabs(ca[k]) <= FINITE_MAX && fabs(cb[k]) <= FINITE_MAX;

@@ -7,18 +7,18 @@
 // the lowest truncated cost, then the lowest number.  The reference has no such step.  include/mpl_hip.h states the five steps;
 // tests/relative_pose_cases.py restates them in numpy.
 //
-// Three launches in the layout of locate_cameras.hip, all float64 on the float32 inputs:
+// Three launches on the scaffold of consensus.hpp, which locate_cameras.hip shares, all float64 on the float32 inputs:
 //   1. relative_prepare_kernel, one workgroup per pair: which slots take part, their undistorted pixels, normalised coordinates and
 //      weight into the workspace; their count, summed in a fixed order.
 //   2. relative_hypotheses_kernel, one lane per hypothesis, one wave per workgroup.  What the solver indexes by a loop counter -- the
 //      14 x 9 system of the Jacobi, the 10 x 20 elimination, the Sturm chain, the roots -- is 249 doubles a lane and lives in LDS,
-//      lane-interleaved as in locate_cameras.hip (125 KiB per wave), not in scratch.  The candidates are scored one after the other,
+//      lane-interleaved (Strided of hestenes.hpp; 125 KiB per wave), not in scratch.  The candidates are scored one after the other,
 //      the records staged 64 at a time in LDS; a lane sums its cost over the slots in their order, so the bits do not depend on how
 //      the hypotheses are dealt to workgroups.
 //   3. relative_select_kernel, one workgroup per pair: the lexicographic winner, its pose, records, inlier mask, count and error.
 // No atomics, nothing read back, no synchronisation.
 #include "common.hpp"
-#include "detrng.hpp"
+#include "consensus.hpp"
 #include "five_point.hpp"
 #include "reprojection.hpp"
 
@@ -26,12 +26,12 @@ namespace mpl {
 
 namespace {
 
-constexpr int RPOSE_LANES = 64;          // hypotheses of one workgroup of the hypothesis kernel: one wave
-constexpr int RPOSE_TILE = 64;           // slots staged in LDS at a time: one per lane
-constexpr int RPOSE_ATTEMPTS = 16, RPOSE_MIN_INLIERS = 6;
-constexpr int RPOSE_THREADS = 256, RPOSE_WAVES = RPOSE_THREADS / 64;
-constexpr int RPOSE_REC = 5;             // a record: u_a (2), u_b (2), w; w = 0: takes no part
-constexpr int RPOSE_LDS = (fivept::FP_DOUBLES * RPOSE_LANES + RPOSE_TILE * RPOSE_REC) * 8;
+using consensus::LANES;
+using consensus::THREADS;
+using consensus::WAVES;
+
+constexpr int RPOSE_REC = 5;             // a record, doubles: u_a (2), u_b (2), w; w = 0: takes no part
+constexpr int RPOSE_LDS = (fivept::FP_DOUBLES * LANES + consensus::TILE * RPOSE_REC) * 8;
 
 // The workspace of a pair, in doubles: a header | the records (N,5) | y_a, y_b (N,4)
 enum { RPOSE_COUNT = 0, RPOSE_USABLE = 1, RPOSE_HDR = 8 };
@@ -103,37 +103,12 @@ __device__ __forceinline__ double rpose_scaled_dot3(double s, double a0, double 
     return s * d;
 }
 
-// the sums of a workgroup of RPOSE_THREADS: down each wave by shuffles, then across the waves in their order; every thread gets them
-template <int K>
-__device__ __forceinline__ void rpose_block_sum(double (&a)[K], double (*sh_part)[2], double* sh_tot) {
-    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) a[k] += __shfl_down(a[k], off, 64);
-    }
-    __syncthreads();                                     // the last read of sh_tot is over
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) sh_part[wave][k] = a[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < K) {
-        double r = sh_part[0][threadIdx.x];
-        for (int w = 1; w < RPOSE_WAVES; ++w) r += sh_part[w][threadIdx.x];
-        sh_tot[threadIdx.x] = r;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; ++k) a[k] = sh_tot[k];
-}
-
 }  // namespace
 
 // ---- 1. participation, undistorted pixels, normalised coordinates, weights and their count
 template <bool LENS>
-__global__ __launch_bounds__(RPOSE_THREADS) void relative_prepare_kernel(const RelativeParams p) {
-    __shared__ double sh_cam[2][21], sh_part[RPOSE_WAVES][2], sh_tot[2];
+__global__ __launch_bounds__(THREADS) void relative_prepare_kernel(const RelativeParams p) {
+    __shared__ double sh_cam[2][21], sh_part[WAVES][2], sh_tot[2];
     const unsigned q = blockIdx.x, tid = threadIdx.x;
     const unsigned va = p.va[q], vb = p.vb[q];
     if (tid < 64) {
@@ -148,10 +123,7 @@ __global__ __launch_bounds__(RPOSE_THREADS) void relative_prepare_kernel(const R
         ca[k] = sh_cam[0][k];
         cb[k] = sh_cam[1][k];
     }
-    const Distortion da{LENS ? sh_cam[0][16] : 0.0, LENS ? sh_cam[0][17] : 0.0, LENS ? sh_cam[0][18] : 0.0, LENS ? sh_cam[0][19] : 0.0,
-                        LENS ? sh_cam[0][20] : 0.0};
-    const Distortion db{LENS ? sh_cam[1][16] : 0.0, LENS ? sh_cam[1][17] : 0.0, LENS ? sh_cam[1][18] : 0.0, LENS ? sh_cam[1][19] : 0.0,
-                        LENS ? sh_cam[1][20] : 0.0};
+    const Distortion da = distortion_from<LENS>(sh_cam[0] + 16), db = distortion_from<LENS>(sh_cam[1] + 16);
     bool finite = true;                                  // of the records, only the intrinsics are read
 #pragma unroll
     for (int k = 0; k < 4; ++k) finite = finite && fabs(ca[k]) <= FINITE_MAX && fabs(cb[k]) <= FINITE_MAX;
@@ -159,7 +131,7 @@ __global__ __launch_bounds__(RPOSE_THREADS) void relative_prepare_kernel(const R
     double* yv = rpose_y(p, q);
 
     double a[1] = {0.0};
-    for (unsigned i = tid; i < p.N; i += RPOSE_THREADS) {
+    for (unsigned i = tid; i < p.N; i += THREADS) {
         const unsigned b = i / p.J, j = i - b * p.J;
         const unsigned oa = (b * p.V + va) * p.J + j, ob = (b * p.V + vb) * p.J + j;      // below 2^30, so twice it fits 32 bits
         const double wa = p.conf ? (double)p.conf[oa] : 1.0, wb = p.conf ? (double)p.conf[ob] : 1.0;
@@ -181,7 +153,7 @@ __global__ __launch_bounds__(RPOSE_THREADS) void relative_prepare_kernel(const R
         y[3] = part ? (ub1 - cb[3]) / cb[1] : 0.0;
         if (part) a[0] += 1.0;
     }
-    rpose_block_sum(a, sh_part, sh_tot);
+    consensus::block_sum(a, sh_part, sh_tot);
     if (tid == 0) {
         double* hdr = rpose_header(p, q);
         hdr[RPOSE_COUNT] = a[0];
@@ -192,55 +164,28 @@ __global__ __launch_bounds__(RPOSE_THREADS) void relative_prepare_kernel(const R
 }
 
 // ---- 2. one lane per hypothesis: sample, solve, score every candidate
-__global__ __launch_bounds__(RPOSE_LANES) void relative_hypotheses_kernel(const RelativeParams p) {
+__global__ __launch_bounds__(LANES) void relative_hypotheses_kernel(const RelativeParams p) {
     extern __shared__ __attribute__((aligned(16))) double rpose_lds[];
-    const fivept::Strided<RPOSE_LANES> mem{rpose_lds + threadIdx.x};
-    double* tile = rpose_lds + fivept::FP_DOUBLES * RPOSE_LANES;
+    const Strided<LANES> mem{rpose_lds + threadIdx.x};
+    double* tile = rpose_lds + fivept::FP_DOUBLES * LANES;
     __shared__ double sh_k[8], sh_hdr[RPOSE_HDR];
-    const unsigned lane = threadIdx.x, q = blockIdx.y, h = blockIdx.x * RPOSE_LANES + lane;
+    const unsigned lane = threadIdx.x, q = blockIdx.y, h = blockIdx.x * LANES + lane;
     if (lane < 4) sh_k[lane] = p.cams[(size_t)p.va[q] * 16 + lane];
     else if (lane < 8) sh_k[lane] = p.cams[(size_t)p.vb[q] * 16 + (lane - 4)];
     else if (lane >= 32 && lane < 32 + RPOSE_HDR) sh_hdr[lane - 32] = rpose_header(p, q)[lane - 32];
     __syncthreads();
-    const bool live = h < p.H;
-    const double nan = __builtin_nan("");
-    double* pose_out = p.poses + ((size_t)q * p.H + h) * 12;
-    double* score_out = p.scores + ((size_t)q * p.H + h) * 2;
+    const consensus::Hypothesis hyp = consensus::hypothesis_at(p.poses, p.scores, q, p.H, h);
     // a pair that has no five correspondences: every hypothesis is void (the same for the whole workgroup)
     if (sh_hdr[RPOSE_USABLE] == 0.0) {
-        if (live) {
-            for (int k = 0; k < 12; ++k) pose_out[k] = nan;
-            score_out[0] = 0.0;
-            score_out[1] = __builtin_inf();
-            p.roots[(size_t)q * p.H + h] = 0;
-        }
+        hyp.write_void();
+        if (hyp.live) p.roots[(size_t)q * p.H + h] = 0;
         return;
     }
     const double* rec = rpose_records(p, q);
     const double* yv = rpose_y(p, q);
 
-    // five distinct participating slots; a lane beyond H draws like any other (every slot is below N) and writes nothing
-    bool ok = true;
     unsigned pick[fivept::FP_SAMPLE];
-    const unsigned long long key = p.keys[q];
-#pragma unroll
-    for (int k = 0; k < fivept::FP_SAMPLE; ++k) {
-        bool got = false;
-        unsigned nk = 0;
-        for (int a = 0; a < RPOSE_ATTEMPTS; ++a) {
-            const unsigned n =
-                (unsigned)(detrng_draw(key, ((unsigned long long)h * fivept::FP_SAMPLE + k) * RPOSE_ATTEMPTS + a) * (double)p.N);
-            bool good = !got && rec[RPOSE_REC * (size_t)n + 4] > 0.0;
-#pragma unroll
-            for (int i = 0; i < k; ++i) good = good && n != pick[i];
-            if (good) {
-                got = true;
-                nk = n;
-            }
-        }
-        pick[k] = nk;
-        ok = ok && got;
-    }
+    const bool ok = consensus::draw_distinct(p.keys[q], h, p.N, [rec](unsigned n) { return rec[RPOSE_REC * (size_t)n + 4] > 0.0; }, pick);
     double ya[fivept::FP_SAMPLE][2], yb[fivept::FP_SAMPLE][2];
 #pragma unroll
     for (int i = 0; i < fivept::FP_SAMPLE; ++i) {
@@ -259,7 +204,7 @@ __global__ __launch_bounds__(RPOSE_LANES) void relative_hypotheses_kernel(const 
     double best_pose[12], best_cost = __builtin_inf();
     int best_count = -1;
 #pragma unroll
-    for (int k = 0; k < 12; ++k) best_pose[k] = nan;
+    for (int k = 0; k < 12; ++k) best_pose[k] = __builtin_nan("");
 #pragma unroll 1
     for (int cand = 0; cand < fivept::FP_MAX_ROOTS; ++cand) {
         if (!__any(cand < n_roots)) break;                           // the same for the whole wave: the barriers below are reached by all
@@ -276,97 +221,44 @@ __global__ __launch_bounds__(RPOSE_LANES) void relative_hypotheses_kernel(const 
         for (int k = 0; k < 12; ++k) pose[k] = 0.0;
         const bool valid = mine && fivept::essential_at(mem, basis, Bz, z, E) && fivept::pose_of(E, sa, sb, pose);
         rpose_fundamental(pose, sh_k, sh_k + 4, F);
-        double cost = 0.0;
-        int count = 0;
-        for (unsigned base = 0; base < p.N; base += RPOSE_TILE) {
-            __syncthreads();                             // the tile before is read
-            if (base + lane < p.N) {
-                const double* g = rec + RPOSE_REC * (size_t)(base + lane);
-#pragma unroll
-                for (int k = 0; k < RPOSE_REC; ++k) tile[RPOSE_REC * lane + k] = g[k];
-            }
-            __syncthreads();
-            const unsigned n = min((unsigned)RPOSE_TILE, p.N - base);
-            for (unsigned i = 0; i < n; ++i) {
-                const double* r = tile + RPOSE_REC * i;  // the same address in every lane
-                const double w = r[4];
-                if (!(w > 0.0)) continue;
-                const double d2 = rpose_sampson2(F, r[0], r[1], r[2], r[3]);
-                const bool in = d2 <= p.tau2;
-                count += in ? 1 : 0;
-                cost += w * (in ? d2 : p.tau2);
-            }
-        }
-        if (valid && (count > best_count || (count == best_count && cost < best_cost))) {
-            best_count = count;
-            best_cost = cost;
+        const auto sampson2 = [&F](const double* r, bool& counts) {
+            counts = true;                               // a slot behind a camera has a distance like any other
+            return rpose_sampson2(F, r[0], r[1], r[2], r[3]);
+        };
+        const consensus::Score sc = consensus::score_tiled<double, RPOSE_REC, double>(rec, p.N, tile, p.tau2, sampson2);
+        if (valid && (sc.count > best_count || (sc.count == best_count && sc.cost < best_cost))) {
+            best_count = sc.count;
+            best_cost = sc.cost;
 #pragma unroll
             for (int k = 0; k < 12; ++k) best_pose[k] = pose[k];
         }
     }
-    if (live) {
-        const bool found = best_count >= 0;
+    if (hyp.live) {
 #pragma unroll
-        for (int k = 0; k < 12; ++k) pose_out[k] = best_pose[k];
-        score_out[0] = found ? (double)best_count : 0.0;
-        score_out[1] = found ? best_cost : __builtin_inf();
+        for (int k = 0; k < 12; ++k) hyp.pose[k] = best_pose[k];
         p.roots[(size_t)q * p.H + h] = n_roots;
     }
+    hyp.write_score(best_count >= 0, best_count, best_cost);
 }
 
 // ---- 3. the winner of a pair, its pose, records, mask, count and error
-__global__ __launch_bounds__(RPOSE_THREADS) void relative_select_kernel(const RelativeParams p) {
-    __shared__ double sh_k[8], sh_part[RPOSE_WAVES][2], sh_tot[2], sh_usable;
-    __shared__ double sh_cnt[RPOSE_WAVES], sh_cost[RPOSE_WAVES];
-    __shared__ int sh_h[RPOSE_WAVES];
-    const unsigned q = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+__global__ __launch_bounds__(THREADS) void relative_select_kernel(const RelativeParams p) {
+    __shared__ double sh_k[8], sh_part[WAVES][2], sh_tot[2], sh_usable;
+    const unsigned q = blockIdx.x, tid = threadIdx.x;
     if (tid < 4) sh_k[tid] = p.cams[(size_t)p.va[q] * 16 + tid];
     else if (tid < 8) sh_k[tid] = p.cams[(size_t)p.vb[q] * 16 + (tid - 4)];
     else if (tid == 32) sh_usable = rpose_header(p, q)[RPOSE_USABLE];
     __syncthreads();
-
-    // most inliers, then the lowest cost, then the lowest number, among the hypotheses that are not void
-    double bc = -1.0, be = __builtin_inf();
-    int bh = -1;
-    if (sh_usable != 0.0) {
-        const double* sc = p.scores + (size_t)q * p.H * 2;
-        for (unsigned h = tid; h < p.H; h += RPOSE_THREADS) {
-            const double cn = sc[2 * (size_t)h], e = sc[2 * (size_t)h + 1];
-            if (!(e <= FINITE_MAX)) continue;
-            if (bh < 0 || cn > bc || (cn == bc && e < be)) {
-                bc = cn; be = e; bh = (int)h;
-            }
-        }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const double oc = __shfl_down(bc, off, 64), oe = __shfl_down(be, off, 64);
-        const int oh = __shfl_down(bh, off, 64);
-        if (oh >= 0 && (bh < 0 || oc > bc || (oc == bc && (oe < be || (oe == be && oh < bh))))) {
-            bc = oc; be = oe; bh = oh;
-        }
-    }
-    if (lane == 0) {
-        sh_cnt[wave] = bc; sh_cost[wave] = be; sh_h[wave] = bh;
-    }
-    __syncthreads();
-    bc = sh_cnt[0]; be = sh_cost[0]; bh = sh_h[0];
-    for (int w = 1; w < RPOSE_WAVES; ++w) {
-        const double oc = sh_cnt[w], oe = sh_cost[w];
-        const int oh = sh_h[w];
-        if (oh >= 0 && (bh < 0 || oc > bc || (oc == bc && (oe < be || (oe == be && oh < bh))))) {
-            bc = oc; be = oe; bh = oh;
-        }
-    }
-    const bool located = bh >= 0 && bc >= (double)RPOSE_MIN_INLIERS;
+    const consensus::Winner best = consensus::select_winner(p.scores, q, p.H, sh_usable != 0.0);
+    const bool located = best.located();
 
     double pose[12], F[9];
 #pragma unroll
-    for (int k = 0; k < 12; ++k) pose[k] = located ? p.poses[((size_t)q * p.H + (unsigned)bh) * 12 + k] : 0.0;
+    for (int k = 0; k < 12; ++k) pose[k] = located ? p.poses[((size_t)q * p.H + (unsigned)best.h) * 12 + k] : 0.0;
     rpose_fundamental(pose, sh_k, sh_k + 4, F);
     const double* rec = rpose_records(p, q);
     double a[2] = {0.0, 0.0};                            // sum d^2 over the inliers, and their count
-    for (unsigned i = tid; i < p.N; i += RPOSE_THREADS) {
+    for (unsigned i = tid; i < p.N; i += THREADS) {
         const unsigned b = i / p.J, j = i - b * p.J;
         const double* r = rec + RPOSE_REC * (size_t)i;
         bool in = false;
@@ -380,7 +272,7 @@ __global__ __launch_bounds__(RPOSE_THREADS) void relative_select_kernel(const Re
         }
         p.out_inliers[((size_t)b * p.P + q) * p.J + j] = in ? 1.0f : 0.0f;
     }
-    rpose_block_sum(a, sh_part, sh_tot);
+    consensus::block_sum(a, sh_part, sh_tot);
     if (tid == 0) {
         const double nan = __builtin_nan("");
         double* ra = p.out_cams + (size_t)q * 32;
@@ -405,14 +297,14 @@ __global__ __launch_bounds__(RPOSE_THREADS) void relative_select_kernel(const Re
             p.out_direction[(size_t)q * 3 + k] = located ? pose[9 + k] : nan;
         }
         p.out_count[q] = (int)a[1];
-        p.out_best[q] = bh;
+        p.out_best[q] = best.h;
         p.out_error[q] = a[1] > 0.0 ? sqrt(a[0] / a[1]) : nan;
         p.out_status[q] = (unsigned char)(located ? LM_CONVERGED : LM_INVALID);
     }
 }
 
 size_t relative_pose_workspace_bytes(int B, int P, int J) {
-    if (B <= 0 || P <= 0 || J <= 0 || P > MPL_MAX_VIEWS || J > 64 || (long long)B * P * J > (1ll << 30)) return 0;
+    if (!consensus::sizes_ok(B, P, J)) return 0;
     return (size_t)P * (RPOSE_HDR + 9 * (size_t)B * (size_t)J) * sizeof(double);
 }
 
@@ -424,16 +316,13 @@ int launch_relative_pose(const float* pixels, const float* conf, const double* c
     if (!pixels || !cams_dev || !pairs || !keys || !out_rotation || !out_direction || !out_cams || !out_inliers || !out_count || !out_best ||
         !out_error || !out_status || !out_poses || !out_scores || !out_roots)
         return MPL_E_INVALID;
-    if (B <= 0 || V <= 0 || J <= 0 || P <= 0 || V > MPL_MAX_VIEWS || P > MPL_MAX_VIEWS || J > 64 || (long long)B * V * J > (1ll << 30) ||
-        (long long)B * P * J > (1ll << 30))
-        return MPL_E_INVALID;
+    if (!consensus::sizes_ok(B, V, J) || !consensus::sizes_ok(B, P, J)) return MPL_E_INVALID;
     for (int q = 0; q < P; ++q) {
         const int a = pairs[2 * q], b = pairs[2 * q + 1];
         if (a < 0 || a >= V || b < 0 || b >= V || a == b) return MPL_E_INVALID;
     }
-    if (!(threshold > 0.0) || !(threshold <= FINITE_MAX) || !(threshold * threshold <= FINITE_MAX) || hypotheses < 1 || hypotheses > 65536 ||
-        !(baseline > 0.0) || !(baseline <= FINITE_MAX))
-        return MPL_E_UNSUPPORTED;
+    if (const int e = consensus::options_check(threshold, hypotheses)) return e;
+    if (!(baseline > 0.0) || !(baseline <= FINITE_MAX)) return MPL_E_UNSUPPORTED;
     if (!workspace || workspace_bytes < relative_pose_workspace_bytes(B, P, J)) return MPL_E_WORKSPACE;
     RelativeParams p;
     p.px = pixels; p.conf = conf; p.cams = cams_dev; p.dist = dist_dev;
@@ -449,22 +338,9 @@ int launch_relative_pose(const float* pixels, const float* conf, const double* c
         p.vb[q] = (unsigned char)(q < P ? pairs[2 * q + 1] : 0);
         p.keys[q] = q < P ? keys[q] : 0ull;
     }
-    if (const int e = kernel_lds_once<relative_hypotheses_kernel>(RPOSE_LDS, RPOSE_LANES)) return e;
-    const dim3 each((unsigned)P), hyp((p.H + RPOSE_LANES - 1) / RPOSE_LANES, (unsigned)P);
-    {
-        ProfScope prof(MPL_K_FUSE_HEAD, s);
-        if (dist_dev) hipLaunchKernelGGL(relative_prepare_kernel<true>, each, dim3(RPOSE_THREADS), 0, s, p);
-        else hipLaunchKernelGGL(relative_prepare_kernel<false>, each, dim3(RPOSE_THREADS), 0, s, p);
-    }
-    {
-        ProfScope prof(MPL_K_FUSE_HEAD, s);
-        hipLaunchKernelGGL(relative_hypotheses_kernel, hyp, dim3(RPOSE_LANES), RPOSE_LDS, s, p);
-    }
-    {
-        ProfScope prof(MPL_K_FUSE_HEAD, s);
-        hipLaunchKernelGGL(relative_select_kernel, each, dim3(RPOSE_THREADS), 0, s, p);
-    }
-    return hip_check_launch();
+    return consensus::launch<relative_prepare_kernel<true>, relative_prepare_kernel<false>, relative_hypotheses_kernel,
+                             relative_hypotheses_kernel, relative_select_kernel, relative_select_kernel>(dist_dev != nullptr, p.P, p.H,
+                                                                                                         RPOSE_LDS, p, s);
 }
 
 }  // namespace mpl

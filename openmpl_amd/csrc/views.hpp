@@ -44,6 +44,12 @@ __device__ __forceinline__ Distortion distortion_of(const double* dist, int v) {
     return d;
 }
 
+// the five coefficients where a kernel has staged them; without LENS nothing is read and the pinhole folds at compile time
+template <bool LENS>
+__device__ __forceinline__ Distortion distortion_from(const double* five) {
+    return Distortion{LENS ? five[0] : 0.0, LENS ? five[1] : 0.0, LENS ? five[2] : 0.0, LENS ? five[3] : 0.0, LENS ? five[4] : 0.0};
+}
+
 struct Normalized {                          // a point in normalised camera coordinates, x_cam.xy / z
     double x, y;
 };

@@ -439,6 +439,31 @@ def refine_cameras(points: torch.Tensor, pixels: torch.Tensor, conf: Optional[to
     return _refine_cameras(points, pixels, conf, cams, distortion, h, max_iterations, tol, mask)
 
 
+def _consensus_options(huber, refine, threshold, hypotheses, seed):
+    """The options locate_cameras and relative_pose share -> (h, tau, H, seed): `huber` as _refine_options has it and only with
+    `refine`, a positive finite threshold in pixels, 1 .. 65536 hypotheses, an integer seed"""
+    if huber is not None and not refine:
+        raise RuntimeError("huber is an option of the refinement: it needs refine=True")
+    h = _refine_options(huber, 20, 1e-8)[0]
+    try:
+        tau = float(threshold)
+    except (TypeError, ValueError):
+        tau = math.nan
+    if not (tau > 0.0 and math.isfinite(tau)):
+        raise RuntimeError("threshold must be a positive finite number of pixels (got %r)" % (threshold,))
+    try:
+        H = -1 if isinstance(hypotheses, bool) else operator.index(hypotheses)
+    except TypeError:
+        H = -1
+    if not 1 <= H <= 65536:
+        raise RuntimeError("hypotheses must be an integer in [1, 65536] (got %r)" % (hypotheses,))
+    try:
+        seed = -1 if isinstance(seed, bool) else operator.index(seed)
+    except TypeError:
+        raise RuntimeError("seed must be an integer (got %r)" % (seed,))
+    return h, tau, H, seed
+
+
 class CamerasLocated(NamedTuple):
     """what locate_cameras returns"""
     cams: torch.Tensor            # (V,16) float64: the records with the located (refine=True: polished) poses, intrinsics as given
@@ -483,25 +508,7 @@ def locate_cameras(points: torch.Tensor, pixels: torch.Tensor, conf: Optional[to
     refine=True) -> bundle_adjust(fixed=(0, 1)).  Three launches before the polish, no synchronisation, nothing read back, identical
     bits from run to run."""
     from . import detrng
-    if huber is not None and not refine:
-        raise RuntimeError("huber is an option of the refinement: it needs refine=True")
-    h = _refine_options(huber, 20, 1e-8)[0]
-    try:
-        tau = float(threshold)
-    except (TypeError, ValueError):
-        tau = math.nan
-    if not (tau > 0.0 and math.isfinite(tau)):
-        raise RuntimeError("threshold must be a positive finite number of pixels (got %r)" % (threshold,))
-    try:
-        H = -1 if isinstance(hypotheses, bool) else operator.index(hypotheses)
-    except TypeError:
-        H = -1
-    if not 1 <= H <= 65536:
-        raise RuntimeError("hypotheses must be an integer in [1, 65536] (got %r)" % (hypotheses,))
-    try:
-        seed = -1 if isinstance(seed, bool) else operator.index(seed)
-    except TypeError:
-        raise RuntimeError("seed must be an integer (got %r)" % (seed,))
+    h, tau, H, seed = _consensus_options(huber, refine, threshold, hypotheses, seed)
     V = pixels.shape[1] if isinstance(pixels, torch.Tensor) and pixels.ndim == 4 else 0
     mask = _fixed_mask(fixed, V) if V else 0             # a pixels tensor of another form is _observations' to complain about
     (points, pixels, conf), cams, distortion, B, V, J = _observations(points, pixels, conf, cams, distortion)
@@ -664,25 +671,7 @@ def relative_pose(pixels: torch.Tensor, conf: Optional[torch.Tensor], cams: torc
     .cams[0] -> locate_cameras(fixed=(0, 1), refine=True) with those two records in place -> bundle_adjust(fixed=(0, 1)).  Three
     launches before the polish, no synchronisation, nothing read back, identical bits from run to run."""
     from . import detrng
-    if huber is not None and not refine:
-        raise RuntimeError("huber is an option of the refinement: it needs refine=True")
-    h = _refine_options(huber, 20, 1e-8)[0]
-    try:
-        tau = float(threshold)
-    except (TypeError, ValueError):
-        tau = math.nan
-    if not (tau > 0.0 and math.isfinite(tau)):
-        raise RuntimeError("threshold must be a positive finite number of pixels (got %r)" % (threshold,))
-    try:
-        H = -1 if isinstance(hypotheses, bool) else operator.index(hypotheses)
-    except TypeError:
-        H = -1
-    if not 1 <= H <= 65536:
-        raise RuntimeError("hypotheses must be an integer in [1, 65536] (got %r)" % (hypotheses,))
-    try:
-        seed = -1 if isinstance(seed, bool) else operator.index(seed)
-    except TypeError:
-        raise RuntimeError("seed must be an integer (got %r)" % (seed,))
+    h, tau, H, seed = _consensus_options(huber, refine, threshold, hypotheses, seed)
     base = _baseline(baseline)
     V = pixels.shape[1] if isinstance(pixels, torch.Tensor) and pixels.ndim == 4 else 0
     flat = _pairs(pairs, V) if V else []                 # a pixels tensor of another form is _observations' to complain about
