@@ -92,3 +92,53 @@ def test_host_stager_reuse_and_short_last_batch():
     with pytest.raises(RuntimeError):
         big = detrng.make_inputs(49, 4, seed=5)
         st.stage(*([torch.from_numpy(x) for x in lst] for lst in big))
+
+
+# ---- prepare_inputs against the float64 oracle at its thread-count edges ---------------------------------------------------------
+# prepare_inputs_kernel runs 256 threads per workgroup over B*V*J points: 255 (one short), 256 (exactly one workgroup), 257 (one
+# thread of a second), 513 (one thread of a third), the envelope corner V = 32 / J = 64 and a single point.  Images are not square.
+# Tolerances: those of the golden tests above (the kernel is fp64 rounded once, like the oracle).
+EDGE_SHAPES = {"n255": (5, 3, 17), "n256": (4, 4, 16), "n257": (257, 1, 1), "n513": (19, 3, 9), "v32_j64": (1, 32, 64), "one": (1, 1, 1)}
+EDGE_WH = (1280.0, 720.0)
+
+
+def edge_case(name):
+    B, V, J = EDGE_SHAPES[name]
+    rs = np.random.RandomState(sorted(EDGE_SHAPES).index(name))
+    w, h = EDGE_WH
+    px = (rs.uniform(0.0, 1.0, (B, V, J, 2)) * np.array([w, h])).astype(np.float32)
+    conf = rs.uniform(0.0, 1.0, (B, V, J)).astype(np.float32)
+    cams = np.zeros((V, 16))
+    for v in range(V):
+        q, _ = np.linalg.qr(rs.randn(3, 3))
+        cams[v] = np.concatenate([[1100.0 + 40 * rs.randn(), 1150.0 + 40 * rs.randn(), w / 2 + 10 * rs.randn(), h / 2 + 10 * rs.randn()],
+                                  (q * np.sign(np.linalg.det(q))).reshape(-1), 4.0 * rs.randn(3)])
+    return px, conf, cams
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", sorted(EDGE_SHAPES))
+def test_prepare_inputs_against_oracle_at_thread_count_edges(name):
+    """Removing `if (idx >= total) return` from prepare_inputs_kernel is seen by tests/test_memory_contract_gpu.py (cases n255,
+    n257, n513: the tail threads write behind the last view's tensors); this test holds the values of the last live thread."""
+    from openmpl_amd.inputs import prepare_inputs
+    px, conf, cams = edge_case(name)
+    B, V, J = EDGE_SHAPES[name]
+    w, h = EDGE_WH
+    dpx, dconf, dcams = torch.from_numpy(px).cuda(), torch.from_numpy(conf).cuda(), torch.from_numpy(cams).cuda()
+    for ni in (True, False):
+        for nc in (True, False):
+            op, orr, oc = io.prepare_inputs(px, conf, cams, w, h, ni, nc)
+            p, r, c = prepare_inputs(dpx, dconf, dcams, (w, h), ni, nc)
+            assert len(p) == len(r) == len(c) == V
+            for v in range(V):
+                assert p[v].shape == (B, J, 3) and r[v].shape == (B, J, 3) and c[v].shape == (B, 1, 3)
+                np.testing.assert_allclose(p[v].cpu().numpy(), op[v], rtol=2e-7, atol=2e-7)
+                np.testing.assert_allclose(r[v].cpu().numpy(), orr[v], rtol=3e-7, atol=5e-7)
+                np.testing.assert_array_equal(c[v].cpu().numpy(), oc[v])
+            # conf=None is the call with explicit ones, bit for bit
+            pn, rn, cn = prepare_inputs(dpx, None, dcams, (w, h), ni, nc)
+            p1, r1, c1 = prepare_inputs(dpx, torch.ones_like(dconf), dcams, (w, h), ni, nc)
+            for a, b in zip(pn + rn + cn, p1 + r1 + c1):
+                assert torch.equal(a, b)
+            assert all(bool((t[..., 2] == 1).all()) for t in pn)
