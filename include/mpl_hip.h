@@ -941,6 +941,67 @@ int mpl_refine_poses(const float *points, const float *pixels, const float *conf
                      float *out_bone_error, double *out_cost0, double *out_cost, int *out_iterations, unsigned char *out_status,
                      void *stream);
 
+/* ---- temporal smoothing of pose tracks, csrc/smooth_tracks.hip.  Every estimator above works on one frame; this call works along
+ * the time axis of a batch in frame order.  points (T,J,3) float32 are the poses of n_segments sequences, frame after frame;
+ * segments (host, n_segments ints >= 1 that sum to frames) are their lengths and seg_offsets_dev (device, n_segments + 1 int32) the
+ * prefix sums of that list, 0 first and `frames` last.  A track is one joint of one segment; no term crosses a segment boundary.
+ * Participation: frame t of a track takes part when its three coordinates are finite and its weight (weight (T,J) float32, NULL:
+ * all ones) is finite and > 0, the rule of takes_part; everything else is a gap.
+ * Cost, per track, Y the given points, T the segment's length:
+ *   E(X) = sum_{t takes part} w_t rho(|X_t - Y_t|^2) + smoothness * sum_t |D^order X|_t^2
+ * D^1 X_t = X_t+1 - X_t (t = 0 .. T-2), D^2 X_t = X_t+1 - 2 X_t + X_t-1 (t = 1 .. T-2); rho(s) = s, or with huber = h > 0 (world
+ * units, on the 3D distance) s up to h^2 and 2 h sqrt(s) - h^2 beyond; a huber that is <= 0 or not finite is the plain mode.  The
+ * three axes share the weights and so one matrix.
+ * Plain mode: one solve of (W + smoothness D^T D) X = W Y, status 0, iterations 1, cost0 = cost = E(X).
+ * Huber mode: iteratively reweighted least squares.  Solve k+1 is the same system with w'_t = w_t min(1, h / |X^k_t - Y_t|), the
+ * first with w' = w; cost0 = E after the first solve.  extent = the largest over the three axes of (max - min of Y over the frames
+ * that take part).  After the first solve: converged if extent == 0.  Then, until stopped: capped (1) if `iterations` ==
+ * max_iterations; solve; if E did not fall strictly, the earlier iterate is kept and the track has converged (0); else the new
+ * iterate is taken, and the track has converged (0) if max_t |X^k+1_t - X^k_t|_inf <= step_tolerance * extent, over all frames.
+ * out_cost <= out_cost0 by construction.
+ * Passed through (2): max_iterations == 0, or fewer than `order` frames take part (the system is singular).  The points are
+ * returned bit for bit, the residual is 0 at frames that take part, both costs are 0 and iterations is 0.
+ * Status 3 (LM_INVALID) is never written: every track either has a positive definite system or passes through, and no input
+ * value makes a track invalid (a smoothness so large that w + smoothness c rounds the weights away still leaves an SPD band).
+ * Outputs, every frame of every track written: out_points (T,J,3) the minimiser, gaps included (a gap is interpolated by the
+ * penalty, linearly at order 1 and by a cubic at order 2, and extrapolated by its null space: constant, straight line);
+ * out_residual (T,J) = |X_t - Y_t|, NaN at gaps; out_irls (T,J) = min(1, h / |X_t - Y_t|) at the returned points, 1 in the plain
+ * mode and where a track passed through, 0 at gaps; out_cost0, out_cost (S,J) float64; out_iterations (S,J) the solves made;
+ * out_status (S,J) bytes.  out_points64 (T,J,3) float64, may be NULL: the points before their rounding.
+ * Method: one wave (MPL_SMOOTH_LANES lanes) per track, grid (n_segments, joints).  A segment of at most MPL_SMOOTH_SINGLE_MAX
+ * frames is solved by one lane (a pentadiagonal L D L^T).  A longer one is cut into blocks of
+ * max(MPL_SMOOTH_CHUNK_MIN, ceil(T / MPL_SMOOTH_LANES)) frames, one per lane -- so the block length grows beyond
+ * MPL_SMOOTH_CHUNK_MIN * MPL_SMOOTH_LANES frames -- with the last two frames of every block but the last as separators: the lanes
+ * factor their interiors, lane 0 solves the Schur complement on the separators in LDS, the lanes back-substitute.  No lane walks
+ * a track longer than MPL_SMOOTH_SINGLE_MAX frames.  Factors and iterates always live in the workspace (there is no LDS-resident
+ * form, hence no third threshold).  fp64 on the fp32 tensors, every output rounded once, sums in a fixed order, no atomics: the
+ * same bits from run to run, and the bits of a track do not depend on what else shares the call.
+ * workspace: mpl_smooth_tracks_workspace_bytes(frames, joints, n_segments) device bytes, 8-byte aligned.
+ * flags: 0, or MPL_SMOOTH_F_SINGLE_LANE, which sends every track to the one-lane form and exists in -DMPL_LAB builds only
+ * (MPL_E_UNSUPPORTED otherwise): the measurement of what the split buys.
+ * Stream-ordered, never synchronises; neither looks at nor sets the device error word.  One launch.
+ * Refusals, before any launch: MPL_E_INVALID: a NULL pointer (weight and out_points64 excepted), frames outside
+ * 1 .. MPL_SMOOTH_MAX_FRAMES, joints outside 1 .. MPL_SMOOTH_MAX_JOINTS, n_segments outside 1 .. frames, a segment outside
+ * 1 .. MPL_SMOOTH_MAX_SEGMENT, segments that do not sum to frames, an order other than 1 or 2, an unknown flag;
+ * MPL_E_UNSUPPORTED: a smoothness that is not finite and > 0, max_iterations outside 0 .. 1000, a step_tolerance that is negative
+ * or not finite; MPL_E_WORKSPACE: workspace NULL, misaligned or too small.  The kernel trusts seg_offsets_dev to be the prefix
+ * sums of `segments`; a track whose two offsets do not describe 1 .. MPL_SMOOTH_MAX_SEGMENT frames inside the tensors is left
+ * unwritten. */
+#define MPL_SMOOTH_LANES 64
+#define MPL_SMOOTH_SINGLE_MAX 32        /* up to here one lane solves the track */
+#define MPL_SMOOTH_CHUNK_MIN 8          /* the shortest block of a split track: six interior frames and two separators */
+#define MPL_SMOOTH_MAX_SEGMENT 65536
+#define MPL_SMOOTH_MAX_FRAMES (1 << 24)
+#define MPL_SMOOTH_MAX_JOINTS 64
+#define MPL_SMOOTH_WS_DOUBLES 18        /* workspace planes per frame and joint: 3 factor, 2 column, 3 right side, 2 x 3 iterate, 4 input */
+#define MPL_SMOOTH_F_SINGLE_LANE 1u
+size_t mpl_smooth_tracks_workspace_bytes(long long frames, int joints, int n_segments); /* 0 outside the limits */
+int mpl_smooth_tracks(const float *points, const float *weight, const int *segments, const int *seg_offsets_dev, int n_segments,
+                      long long frames, int joints, double smoothness, int order, double huber, int max_iterations,
+                      double step_tolerance, unsigned flags, void *workspace, size_t workspace_bytes, float *out_points,
+                      float *out_residual, float *out_irls, double *out_cost0, double *out_cost, int *out_iterations,
+                      unsigned char *out_status, double *out_points64, void *stream);
+
 /* ---- Procrustes alignment of predicted poses onto their targets, csrc/procrustes.hip: the transform behind PA-MPJPE (Protocol
  * 2), in place of lib/utils/pose_utils.py:61-143 PoseUtils.procrustes (a numpy port of MATLAB's procrustes, one 3x3 SVD per pose
  * on the host, which would force all_preds back to the host).  One launch aligns `batch` poses: target A and prediction B, both

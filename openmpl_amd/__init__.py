@@ -17,7 +17,7 @@ def __getattr__(name):
         return PoseEvaluator
     if name in ("triangulate_rays", "triangulate_rays_robust", "triangulate_pixels", "epipolar_errors", "consistency_weights", "refine_points",
                 "reprojection_errors", "refine_cameras", "locate_cameras", "relative_pose", "refine_relative_pose", "bundle_adjust", "refine_poses",
-                "bone_lengths"):
+                "bone_lengths", "smooth_tracks"):
         from . import geometry
         return getattr(geometry, name)
     if name == "procrustes_align":

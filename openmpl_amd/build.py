@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libmpl_hip.so")
-SOURCES = ["api.hip", "spt.hip", "spt_native.hip", "spt_packed.hip", "d32_blocks.hip", "spt_any.hip", "ln_gemm.hip", "h2_gemm.hip", "h2n_gemm.hip", "h2d_gemm.hip", "b1_gemm.hip", "b1_any.hip", "sm_stack.hip", "token_attention.hip", "token_attention_wide.hip", "fuse_head.hip", "heads.hip", "metrics.hip", "evaluate.hip", "inputs.hip", "distortion.hip", "heatmaps.hip", "heatmap_render.hip", "rpsm.hip", "synth.hip", "geometry.hip", "refine.hip", "refine_cameras.hip", "refine_poses.hip", "locate_cameras.hip", "relative_pose.hip", "refine_relative_pose.hip", "procrustes.hip"]
+SOURCES = ["api.hip", "spt.hip", "spt_native.hip", "spt_packed.hip", "d32_blocks.hip", "spt_any.hip", "ln_gemm.hip", "h2_gemm.hip", "h2n_gemm.hip", "h2d_gemm.hip", "b1_gemm.hip", "b1_any.hip", "sm_stack.hip", "token_attention.hip", "token_attention_wide.hip", "fuse_head.hip", "heads.hip", "metrics.hip", "evaluate.hip", "inputs.hip", "distortion.hip", "heatmaps.hip", "heatmap_render.hip", "rpsm.hip", "synth.hip", "geometry.hip", "refine.hip", "refine_cameras.hip", "refine_poses.hip", "smooth_tracks.hip", "locate_cameras.hip", "relative_pose.hip", "refine_relative_pose.hip", "procrustes.hip"]
 HEADERS = [os.path.join(CSRC, "common.hpp"), os.path.join(CSRC, "gemm_common.hpp"), os.path.join(CSRC, "h2_phase.hpp"), os.path.join(CSRC, "h2_stack_walk.inc"), os.path.join(CSRC, "fuse_head.hpp"), os.path.join(CSRC, "spt_stage.hpp"), os.path.join(CSRC, "spt_pack.hpp"), os.path.join(CSRC, "views.hpp"), os.path.join(CSRC, "reprojection.hpp"), os.path.join(CSRC, "detrng.hpp"), os.path.join(CSRC, "hestenes.hpp"), os.path.join(CSRC, "consensus.hpp"), os.path.join(CSRC, "five_point.hpp"), os.path.join(os.path.dirname(HERE), "include", "mpl_hip.h")]
 ARCH = "gfx950"
 

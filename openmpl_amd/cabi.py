@@ -101,6 +101,17 @@ RENDER_MODES = {"reference": 0, "subpixel": 1}
 # mpl_rpsm(): the launches a call issues (MPL_RPSM_* of mpl_hip.h); anything but RPSM_ALL is a measurement
 RPSM_UNARY, RPSM_LEVELS, RPSM_FINAL, RPSM_ALL = 1, 2, 4, 7
 
+# mpl_smooth_tracks(): the thresholds and limits of the kernel (MPL_SMOOTH_* of mpl_hip.h); tests derive their lengths from these
+SMOOTH_LANES, SMOOTH_SINGLE_MAX, SMOOTH_CHUNK_MIN, SMOOTH_MAX_SEGMENT, SMOOTH_MAX_FRAMES, SMOOTH_MAX_JOINTS = 64, 32, 8, 65536, 1 << 24, 64
+SMOOTH_F_SINGLE_LANE = 1
+
+
+def smooth_thresholds():
+    """the segment lengths at which mpl_smooth_tracks changes its path: the last length one lane solves, and the last length at
+    which the blocks of a split track have their shortest form"""
+    return (SMOOTH_SINGLE_MAX, SMOOTH_CHUNK_MIN * SMOOTH_LANES)
+
+
 # mpl_undistort_points(): the directions (MPL_DISTORT_* of mpl_hip.h)
 DISTORT_REMOVE, DISTORT_APPLY = 0, 1
 
@@ -137,6 +148,8 @@ EXPORTS = ("mpl_hip_abi_version", "mpl_hip_error_string", "mpl_config_supported"
            "mpl_refine_cameras",
            # and the joints of a pose as one body: the same error plus bone-length terms, solved on the tree
            "mpl_refine_poses",
+           # and along the time axis: every (sequence, joint) track smoothed, gaps filled, outlier frames held down
+           "mpl_smooth_tracks_workspace_bytes", "mpl_smooth_tracks",
            # and the step before it: a camera located from scratch by hypothesise-and-score over 6-point resections
            "mpl_locate_cameras_workspace_bytes", "mpl_locate_cameras",
            # and the step before that one: the relative pose of two views from their detections alone, by five-point hypotheses
@@ -336,6 +349,11 @@ def load():
         lib.mpl_refine_poses.restype = C.c_int
         lib.mpl_refine_poses.argtypes = [_fp, _fp, _fp, _fp, _fp, _fp, C.c_longlong, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int,
                                          C.c_double, C.c_double, C.c_int, C.c_double, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp]
+        lib.mpl_smooth_tracks_workspace_bytes.restype = C.c_size_t
+        lib.mpl_smooth_tracks_workspace_bytes.argtypes = [C.c_longlong, C.c_int, C.c_int]
+        lib.mpl_smooth_tracks.restype = C.c_int
+        lib.mpl_smooth_tracks.argtypes = [_fp, _fp, C.POINTER(C.c_int), _fp, C.c_int, C.c_longlong, C.c_int, C.c_double, C.c_int, C.c_double,
+                                          C.c_int, C.c_double, C.c_uint, _fp, C.c_size_t, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp]
         lib.mpl_locate_cameras_workspace_bytes.restype = C.c_size_t
         lib.mpl_locate_cameras_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
         lib.mpl_locate_cameras.restype = C.c_int

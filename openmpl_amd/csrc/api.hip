@@ -967,6 +967,21 @@ int mpl_refine_poses(const float* points, const float* pixels, const float* conf
                                out_iterations, out_status, (hipStream_t)stream);
 }
 
+size_t mpl_smooth_tracks_workspace_bytes(long long frames, int joints, int n_segments) {
+    return smooth_tracks_workspace_bytes(frames, joints, n_segments);
+}
+
+int mpl_smooth_tracks(const float* points, const float* weight, const int* segments, const int* seg_offsets_dev, int n_segments,
+                      long long frames, int joints, double smoothness, int order, double huber, int max_iterations,
+                      double step_tolerance, unsigned flags, void* workspace, size_t workspace_bytes, float* out_points,
+                      float* out_residual, float* out_irls, double* out_cost0, double* out_cost, int* out_iterations,
+                      unsigned char* out_status, double* out_points64, void* stream) {
+    clear_stale_hip_error();
+    return launch_smooth_tracks(points, weight, segments, seg_offsets_dev, n_segments, frames, joints, smoothness, order, huber,
+                                max_iterations, step_tolerance, flags, workspace, workspace_bytes, out_points, out_residual, out_irls,
+                                out_cost0, out_cost, out_iterations, out_status, out_points64, (hipStream_t)stream);
+}
+
 size_t mpl_locate_cameras_workspace_bytes(int batch, int views, int joints) { return locate_cameras_workspace_bytes(batch, views, joints); }
 
 int mpl_locate_cameras(const float* points, const float* pixels, const float* conf, const double* cams_dev, const double* dist_dev,

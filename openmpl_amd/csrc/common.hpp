@@ -389,6 +389,13 @@ int launch_refine_poses(const float* points, const float* pixels, const float* c
                         float* out_bone_error, double* out_cost0, double* out_cost, int* out_iterations, unsigned char* out_status,
                         hipStream_t s);
 
+// smooth_tracks.hip: temporal smoothing of pose tracks, one wave per (segment, joint) track (mpl_smooth_tracks); segments: host
+size_t smooth_tracks_workspace_bytes(long long T, int J, int S);
+int launch_smooth_tracks(const float* points, const float* weight, const int* segments, const int* seg_offsets_dev, int S, long long T,
+                         int J, double smoothness, int order, double huber, int max_iterations, double step_tolerance, unsigned flags,
+                         void* ws, size_t ws_bytes, float* out_points, float* out_residual, float* out_irls, double* out_cost0,
+                         double* out_cost, int* out_iterations, unsigned char* out_status, double* out_points64, hipStream_t s);
+
 // locate_cameras.hip: robust resection of every view from known 3D points, hypothesise-and-score (mpl_locate_cameras); keys: host,
 // one detrng stream key per view
 size_t locate_cameras_workspace_bytes(int B, int V, int J);

@@ -14,7 +14,8 @@ bone-length terms on the tree of rpsm.  refine_cameras (mpl_refine_cameras, csrc
 refine_points -- the points given, the camera poses moved --, and bundle_adjust alternates the two.  locate_cameras (mpl_locate_cameras, csrc/locate_cameras.hip) is the step before
 them: a camera located from no pose at all by hypothesise-and-score over 6-point resections.  relative_pose (mpl_relative_pose,
 csrc/relative_pose.hip) is the step before that one: the relative pose of two views from their detections and intrinsics alone, by
-hypothesise-and-score over five-point solutions.
+hypothesise-and-score over five-point solutions.  smooth_tracks (mpl_smooth_tracks, csrc/smooth_tracks.hip) works along the time
+axis of a batch in frame order: every (sequence, joint) track smoothed, its gaps filled, its outlier frames held down.
 """
 from __future__ import annotations
 
@@ -345,6 +346,116 @@ def refine_poses(points: torch.Tensor, pixels: torch.Tensor, conf: Optional[torc
     cabi.launch("refine_poses", dev, points.data_ptr(), pixels.data_ptr(), ptr(conf), cams.data_ptr(), ptr(distortion),
                 limb_length.data_ptr(), J if limb_length.ndim == 2 else 0, (cabi.C.c_int * J)(*parents), B, V, J, h, bw, max_iterations, tol,
                 *(t.data_ptr() for t in out))
+    return out
+
+
+class TracksSmoothed(NamedTuple):
+    """what smooth_tracks returns"""
+    points: torch.Tensor          # (T,J,3) float32: the minimiser, gaps filled
+    residual: torch.Tensor        # (T,J) float32: |X_t - Y_t|, NaN at gaps
+    irls_weight: torch.Tensor     # (T,J) float32: min(1, huber / residual) at the result; 1 in the plain mode, 0 at gaps
+    cost0: torch.Tensor           # (S,J) float64: E after the first solve, in the mode of the call
+    cost: torch.Tensor            # (S,J) float64: E at the result; never above cost0
+    iterations: torch.Tensor      # (S,J) int32: solves made
+    status: torch.Tensor          # (S,J) uint8: 0 converged, 1 capped, 2 passed through
+    points64: Optional[torch.Tensor] = None      # (T,J,3) float64 with return_float64=True: the points before their rounding
+
+
+def _segments(segments, T):
+    """`segments` -> a list of positive ints that sum to T and stay inside the kernel's limits; default one segment"""
+    if segments is None:
+        segments = (T,)
+    if isinstance(segments, torch.Tensor):
+        if segments.device.type != "cpu":
+            raise ValueError("segments is read on the host: pass a sequence of ints or a CPU tensor")
+        segments = segments.tolist()
+    try:
+        seg = [operator.index(n) for n in segments]
+    except TypeError:
+        raise ValueError("segments must be a sequence of ints (got %r)" % (segments,)) from None
+    if not seg or min(seg) < 1:
+        raise ValueError("segments must be positive frame counts (got %r)" % (segments,))
+    if sum(seg) != T:
+        raise ValueError("segments sum to %d, the points have %d frames" % (sum(seg), T))
+    if max(seg) > cabi.SMOOTH_MAX_SEGMENT:
+        raise ValueError("a segment of %d frames: at most %d" % (max(seg), cabi.SMOOTH_MAX_SEGMENT))
+    return seg
+
+
+def smooth_tracks(points: torch.Tensor, weight: Optional[torch.Tensor] = None, *, segments: Optional[Sequence[int]] = None,
+                  smoothness: float, order: int = 2, huber: Optional[float] = None, max_iterations: int = 20,
+                  step_tolerance: float = 1e-6, return_float64: bool = False, _single_lane: bool = False) -> TracksSmoothed:
+    """Pose tracks smoothed along time on the device: jitter taken out, gaps filled, single outlier frames held down.  points
+    (T,J,3) float32: the poses of one or several sequences frame after frame -- what refine_points(...).points,
+    refine_poses(...).points, triangulate_*, rpsm or the model return for a batch in frame order.  weight (T,J) float32 or None (all
+    ones): a confidence, 1 / error**2 of refine_points, a status < 3 mask.  A frame of a joint takes part when its coordinates are
+    finite and its weight is finite and > 0; everything else is a gap.  segments: the frame counts of the sequences, positive ints
+    that sum to T (default (T,)), read on the host; no term crosses a boundary.  Per track (segment, joint) the minimiser of
+
+        E(X) = sum_{t takes part} w_t rho(|X_t - Y_t|^2) + smoothness * sum_t |D^order X|_t^2
+
+    D^1 X_t = X_t+1 - X_t, D^2 X_t = X_t+1 - 2 X_t + X_t-1 inside the segment; rho(s) = s, or with huber = h (world units, on the 3D
+    distance) s up to h^2 and 2 h sqrt(s) - h^2 beyond.  smoothness: finite, > 0; order: 1 or 2; a huber that is None, <= 0 or not
+    finite is the plain mode, as the C ABI reads it; max_iterations (0 .. 1000) and step_tolerance as refine_points checks them.
+    Plain mode: one solve.  Huber mode: iteratively reweighted least squares,
+    w' = w min(1, h / |X - Y|) from the previous iterate, until the largest coordinate step is <= step_tolerance times the extent of
+    the track (its largest coordinate spread over the frames that take part) or the cost stops falling (the earlier iterate is
+    kept); cost0 is E after the first solve, so cost <= cost0.  -> TracksSmoothed(points, residual, irls_weight, cost0, cost,
+    iterations, status): every frame of every track is written.  Gaps get the minimiser's value: interpolated linearly (order 1) or
+    by a cubic (order 2), and continued as a constant or a straight line before the first and after the last frame that takes part.
+    irls_weight is the call's outlier report.  status per track: 0 converged, 1 capped at max_iterations, 2 passed through
+    (max_iterations == 0, or fewer than `order` frames take part: the points bit for bit, residual 0 where a frame takes part, costs
+    0); 3 is never written.  return_float64=True adds points64, the points before their rounding.  One launch, one wave per track,
+    the time axis split among its lanes; no synchronisation; identical bits from run to run, and a track's bits do not depend on
+    which other segments and joints share the call."""
+    _, max_iterations, tol = _refine_options(None, max_iterations, step_tolerance)
+    h = 0.0 if huber is None else float(huber)
+    h = h if (h > 0.0 and math.isfinite(h)) else 0.0           # <= 0, NaN, inf: the plain mode, as the C ABI reads it
+    try:
+        lam = float(smoothness)
+    except (TypeError, ValueError):
+        lam = float("nan")
+    if not (lam > 0.0 and math.isfinite(lam)):
+        raise RuntimeError("smoothness must be a finite number > 0 (got %r)" % (smoothness,))
+    if order not in (1, 2):
+        raise RuntimeError("order must be 1 or 2 (got %r)" % (order,))
+    if not isinstance(points, torch.Tensor):
+        raise RuntimeError("points must be a tensor")
+    if points.ndim != 3 or points.shape[2] != 3 or min(points.shape[:2]) < 1:
+        raise RuntimeError("points: expected shape (T,J,3), got %s" % (tuple(points.shape),))
+    T, J = points.shape[:2]
+    if weight is not None:
+        if not isinstance(weight, torch.Tensor):
+            raise RuntimeError("weight must be a tensor")
+        if tuple(weight.shape) != (T, J):
+            raise RuntimeError("weight: expected shape %s, got %s" % ((T, J), tuple(weight.shape)))
+    if T > cabi.SMOOTH_MAX_FRAMES or J > cabi.SMOOTH_MAX_JOINTS:
+        raise RuntimeError("points of shape %s: at most %d frames and %d joints" % (tuple(points.shape), cabi.SMOOTH_MAX_FRAMES, cabi.SMOOTH_MAX_JOINTS))
+    seg = _segments(segments, T)
+    for what, t in (("points", points), ("weight", weight)):
+        if t is not None and t.dtype != torch.float32:
+            raise RuntimeError("float32 tensors required (%s is %s)" % (what, t.dtype))
+    if points.device.type != "cuda":
+        raise RuntimeError("points must be on the GPU (got %s)" % points.device)
+    dev = points.device
+    if weight is not None and weight.device != dev:
+        raise RuntimeError("weight is on %s, points on %s" % (weight.device, dev))
+    points = points.contiguous()
+    weight = None if weight is None else weight.contiguous()
+    S = len(seg)
+    offsets = [0]
+    for n in seg:
+        offsets.append(offsets[-1] + n)
+    table = torch.empty((S + 1,), dtype=torch.int32, device=dev)
+    table.copy_(torch.tensor(offsets, dtype=torch.int32), non_blocking=False)
+    ws = torch.empty((cabi.load().mpl_smooth_tracks_workspace_bytes(T, J, S),), dtype=torch.uint8, device=dev)
+    f32, f64 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.float64, device=dev)
+    out = TracksSmoothed(torch.empty((T, J, 3), **f32), torch.empty((T, J), **f32), torch.empty((T, J), **f32), torch.empty((S, J), **f64),
+                         torch.empty((S, J), **f64), torch.empty((S, J), dtype=torch.int32, device=dev),
+                         torch.empty((S, J), dtype=torch.uint8, device=dev), torch.empty((T, J, 3), **f64) if return_float64 else None)
+    cabi.launch("smooth_tracks", dev, points.data_ptr(), ptr(weight), (cabi.C.c_int * S)(*seg), table.data_ptr(), S, T, J, lam, order, h,
+                max_iterations, tol, cabi.SMOOTH_F_SINGLE_LANE if _single_lane else 0, ws.data_ptr(), ws.numel(),
+                *(t.data_ptr() for t in out[:7]), ptr(out.points64))
     return out
 
 
