@@ -376,7 +376,9 @@ int mpl_linear(const float *xa, int Ka, const float *xb, int Kb, int M, const fl
  *   joints_px (B,V,J,2) pixel coordinates, conf (B,V,J) or NULL (-> 1), device;
  *   cams_dev device (V,16) float64: fx fy cx cy | R row-major (world->camera) | t (camera centre in world coords);
  *   img_w/img_h = NETWORK.IMAGE_SIZE; normalize_inputs = DATASET.INPUTS_NORMALIZED, normalize_cameras =
- *   DATASET.NORMALIZE_CAMERAS;  poses/rays/centers: host arrays of V device pointers to (B,J,3),(B,J,3),(B,1,3). */
+ *   DATASET.NORMALIZE_CAMERAS;  poses/rays/centers: host arrays of V device pointers to (B,J,3),(B,J,3),(B,1,3).
+ * MPL_E_INVALID: joints_px or cams_dev NULL, a non-positive size or image size, views > MPL_MAX_VIEWS, a NULL table or entry;
+ * MPL_E_UNSUPPORTED: batch * views * joints > 2^30 -- before any launch. */
 int mpl_prepare_inputs(const float *joints_px, const float *conf, const double *cams_dev, int batch, int views,
                        int joints, float img_w, float img_h, int normalize_inputs, int normalize_cameras,
                        float *const *poses, float *const *rays, float *const *centers, void *stream);
@@ -1123,12 +1125,16 @@ int mpl_ln_linear_h2(const float *x, int M, int K, int has_ln, float eps, const 
  * operands: it sets a sticky per-device error word, the poses of that call are NaN, and EVERY later call on the device
  * returns MPL_E_DEVICE until mpl_device_error_clear() -- the reference's convention for a failed forward is a Python
  * exception (SURVEY.md 8b "Error convention"), which is what the binding turns this into.
- * mpl_device_error(dev): the word, 0 = no failure (dev < 0: the current device); no synchronisation, reads pinned memory.  Bits:
- *   1 = lost hand-off / operands packed against other scales (above);
- *   2 = the split-operand SPT engine met a confidence-weighted attention row (confidence_as_attention_uncertainty_weight,
+ * mpl_device_error(dev): the word, 0 = no failure (dev < 0: the current device); no synchronisation, reads pinned memory.  Values:
+ *   1 (bit 0) = lost hand-off / operands packed against other scales (above);
+ *   2 (bit 1) = the split-operand SPT engine met a confidence-weighted attention row (confidence_as_attention_uncertainty_weight,
  *       reference multiview_mpl.py:61-62: the softmax rows are multiplied by the caller's `conf`, which is DATA) beyond the
  *       fp16 window its static scales assume: that sequence's poses are NaN -- never a saturated, plausible-looking pose --
  *       and the caller is pointed at the native-fp32 engine (MPL precision "fp32_mfma"), which has no window.
+ *       Only a FINITE row beyond the window is reported.  A NaN or infinite keypoint or confidence (a missing detection) is
+ *       the caller's data: the reference answers it with NaN poses for that sample, so does every engine here -- that
+ *       sample NaN in every element, every other sample of the batch bit for bit what it is without it -- and the word
+ *       stays 0 (tests/test_nonfinite_gpu.py).
  * mpl_x3_spin_limit(v): test hook.  v & 0xff = log2 of the polls before a wait counts as lost (default 23 ~ 10 s);
  * v >> 8 = fault injection: when > 0, one workgroup of the next launches deserts its team before that GEMM phase, so
  * that the failure path can be exercised deterministically (tests/test_failures_gpu.py). */

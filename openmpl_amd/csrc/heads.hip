@@ -180,7 +180,8 @@ __global__ __launch_bounds__(256) void linear_mfma_kernel(const float* __restric
                 const int m = m0 + 32 * wr + 16 * i + 4 * kq + r;
                 if (m >= M) continue;
                 float v = (acc[i][j][r] + bv) * sc + sh;
-                if (relu) v = fmaxf(v, 0.f);
+                // nn.ReLU keeps a NaN (the pose of a sample with a NaN keypoint is NaN); fmaxf alone returns its other operand, 0
+                if (relu) v = (v == v) ? fmaxf(v, 0.f) : v;
                 y[(size_t)m * ldy + n] = v;
             }
     }

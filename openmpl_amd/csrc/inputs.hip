@@ -50,6 +50,7 @@ int launch_prepare_inputs(const float* px, const float* conf, const double* cams
                           float w, float h, int norm_in, int norm_cam, float* const* poses, float* const* rays, float* const* centers,
                           hipStream_t s) {
     if (!px || !cams_dev || B <= 0 || V <= 0 || J <= 0 || w <= 0 || h <= 0) return MPL_E_INVALID;
+    if ((long long)B * V * J > (1ll << 30)) return MPL_E_UNSUPPORTED;        // the item index is an int
     PrepLensParams p;
     if (const int rc = view_outputs_fill(p.out, poses, rays, centers, V)) return rc;
     p.px = px; p.conf = conf; p.cams = cams_dev; p.dist = dist_dev;

@@ -103,11 +103,11 @@ int launch_row_stats(const float* x, int M, int K, int ldx, float* stats, hipStr
     if (M <= 0 || K <= 0) return MPL_E_INVALID;
     ProfScope prof(MPL_K_ROW_STATS, s);
     if ((K & 3) || (ldx & 3))
-        hipLaunchKernelGGL(row_stats_any_kernel, dim3((M + 3) / 4), dim3(256), 0, s, x, M, K, ldx, ln_slice_len(K), stats);
+        hipLaunchKernelGGL(row_stats_any_kernel, dim3((unsigned)(((long long)M + 3) / 4)), dim3(256), 0, s, x, M, K, ldx, ln_slice_len(K), stats);
     else if (K == 32 && (ldx & 3) == 0)
         hipLaunchKernelGGL(row_stats32_kernel, dim3((int)(((size_t)M * 8 + 255) / 256)), dim3(256), 0, s, x, M, ldx, stats);
     else
-        hipLaunchKernelGGL(row_stats_kernel, dim3((M + 3) / 4), dim3(256), 0, s, x, M, K, ldx, ln_slice_len(K), stats);
+        hipLaunchKernelGGL(row_stats_kernel, dim3((unsigned)(((long long)M + 3) / 4)), dim3(256), 0, s, x, M, K, ldx, ln_slice_len(K), stats);
     return hip_check_launch();
 }
 

@@ -349,7 +349,7 @@ __global__ __launch_bounds__(256) void rpsm_final_kernel(const RpsmParams p) {
 }
 
 size_t rpsm_workspace_bytes(int B, int J, int first_nbins) {
-    if (B <= 0 || J <= 0 || J > RPSM_MAX_J || first_nbins < 2 || first_nbins > 16) return 0;
+    if (B <= 0 || B > (1 << 20) || J <= 0 || J > RPSM_MAX_J || first_nbins < 2 || first_nbins > 16) return 0;
     const size_t cells = (size_t)B * J * first_nbins * first_nbins * first_nbins;
     return cells * sizeof(double) + cells * sizeof(unsigned short);
 }

@@ -467,14 +467,21 @@ __global__ __launch_bounds__(NTHR, 1) void spt3_kernel(const SptParams p) {
                     // the confidence weights are data (reference :61-62 multiplies the softmax rows by whatever `conf` it is
                     // given): only with them can the operand leave the window its static, data-free scale assumes.  That is
                     // reported, never absorbed: the row becomes NaN (so do the poses of its sequence) and the device error word
-                    // gets bit 1 -- the next API call and check_device() raise, pointing at the native-fp32 engine, which has
+                    // gets bit 1 (value 2) -- the next API call and check_device() raise, pointing at the native-fp32 engine, which has
                     // no window.  (Rounds 3-5 clamped to +-65000 here: plausible-looking poses from saturated operands.)
+                    // The report is for a FINITE operand beyond the window.  A row that is NaN or infinite comes from a NaN or
+                    // infinite keypoint or confidence, the caller's data, which the reference answers with NaN poses for that
+                    // sequence: the row becomes NaN all the same, nothing saturated is hidden, and the error word stays clear.
+                    // (fmaxf drops a NaN operand, so `big` is NaN only when all four components are; a non-finite confidence
+                    // makes inv[t], a non-finite keypoint every q / k / v of the sequence non-finite, so a row never mixes a NaN
+                    // component with a finite one beyond the window.)
                     if (weighted) {
                         const float big = fmaxf(fmaxf(fabsf(o[t].x), fabsf(o[t].y)), fmaxf(fabsf(o[t].z), fabsf(o[t].w)));
                         if (!(big <= 65000.f)) {
                             const float qn = __builtin_nanf("");
                             o[t] = float4{qn, qn, qn, qn};
-                            if (p.err_host) __hip_atomic_fetch_or(p.err_host, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                            if (big < __builtin_inff() && p.err_host)
+                                __hip_atomic_fetch_or(p.err_host, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                         }
                     }
                 }

@@ -40,7 +40,7 @@ struct SptParams {
     int c3;  // channel count of the pos_3d_* tensors (d or 2d)
     int spw;  // sequences per workgroup (spt_kernel: 1..16, few sequences spread over the chip; spt3_kernel<SS>: SS)
     int abl;  // MPL_SPT_ABL, laboratory builds only.  spt_kernel: 1 no attention, 2 no GELU, 4 no MFMA phases, 16 cycle counts for the output; spt3_kernel: tools/spt_abl.py
-    unsigned* err_host;  // sticky error word of the device (common.hpp device_error_word): bit 1 = an operand left its fp16 window
+    unsigned* err_host;  // sticky error word of the device (common.hpp device_error_word): bit 1 (value 2) = an operand left its fp16 window
     unsigned char sched[MPL_MAX_APPS];  // layer | weighted << 7
 };
 

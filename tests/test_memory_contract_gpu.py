@@ -400,51 +400,10 @@ def test_pose_metrics(capsys):
 # guarded allocations like `out`, `ws`, `xs` and the staged intermediates, and the workspace is handed over as NaN bytes.  One
 # model per path; the library is asked which path the launch took (mpl_block_stack_last_form, mpl_spt_form) and the test fails if
 # the form it is there for was not reached.  Batches: the smallest the library's own rule sends to the form on this device.
-from tests.golden.cases import CHOSEN, FULL  # noqa: E402
+# The table of models, one per path, is tests/forward_paths.py, which tests/test_nonfinite_gpu.py visits too.
+from tests.forward_paths import DEV, FORWARD_MODELS, _fresh_model, _stack_shape  # noqa: E402
 
-DEV = "cuda:0"
 FORWARD_CALLS = ("mpl_forward", "mpl_spt_tokens", "mpl_block_stack_ex", "mpl_view_norm", "mpl_view_fuse", "mpl_layernorm", "mpl_linear")
-
-
-def _flags(J=17, d=32, H=8, V=4, L=2, **extra):
-    return dict(num_joints=J, embed_dim_ratio=d, num_heads=H, depth=L, num_views=V, **extra)
-
-
-KPTOK = dict(CHOSEN, FPT_blocks_view_keypoint_tokens=True)
-# name: (flags, precision, small-batch engine, stack form wanted (None: no stack), SPT form wanted (a set; None: no SPT), batch or None = search)
-FORWARD_MODELS = {
-    "small_engine_b1": (_flags(V=2, **CHOSEN), "fp32", "auto", "SMALL", {"PACKED"}, 1),
-    "team_rows16_direct": (_flags(V=2, **CHOSEN), "fp32", False, "ROWS16_DIRECT", {"PACKED"}, None),
-    "team_rows16_ring": (_flags(V=2, **FULL), "fp32", False, "ROWS16", {"PACKED"}, None),
-    "team_rows32": (_flags(V=8, **CHOSEN), "fp32", False, "ROWS32", {"PACKED"}, None),
-    "team_whole_tile": (_flags(V=5, **CHOSEN), "fp32", False, "TEAMS", {"PACKED"}, None),
-    "team_pairs": (_flags(V=8, **CHOSEN), "fp32", False, "PAIRS", {"PACKED"}, None),
-    "bf16_team": (_flags(V=4, **CHOSEN), "bf16", False, "TEAMS", {"PACKED"}, None),
-    "j15_unpacked": (_flags(J=15, **CHOSEN), "fp32", False, "UNPACKED", {"ANY"}, 6),
-    "j15_bf16_any": (_flags(J=15, **CHOSEN), "bf16", "auto", "BF16_ANY", {"ANY"}, 6),
-    "grid_d32": (_flags(V=3, **KPTOK), "fp32", "auto", "UNPACKED", {"PACKED"}, 3),
-    "grid_wide_head": (_flags(H=2, V=2, **KPTOK), "fp32", "auto", "UNPACKED", {"ANY"}, 3),
-    "fp32_mfma": (_flags(V=4, **CHOSEN), "fp32_mfma", False, "UNPACKED", {"STAGED", "FRAGS"}, 3),
-    "fuse_any_tail_e640": (_flags(J=20, **CHOSEN), "fp32", False, "UNPACKED", {"ANY"}, 4),
-    "linear_weighted_mean": (_flags(V=3, **dict(CHOSEN, linear_weighted_mean=True)), "fp32", "auto", None, {"PACKED"}, 3),
-    "deep_head": (_flags(V=3, **dict(CHOSEN, deep_head=True, hidden_dim=64)), "fp32", "auto", None, {"PACKED"}, 3),
-    "head_kadkhod": (_flags(V=3, **dict(CHOSEN, head_kadkhod=True, hidden_dim=64)), "fp32", "auto", None, {"PACKED"}, 3),
-}
-
-
-def _fresh_model(flags, prec, small):
-    from openmpl_amd import detrng
-    from openmpl_amd.multiview_mpl import MultiView_MPL
-    m = detrng.fill_module_(MultiView_MPL(**flags), seed=11)
-    assert m._unsupported is None, m._unsupported
-    return m.to(DEV).eval().use_torch_op(False).set_matmul_precision(prec).set_small_batch_engine(small)
-
-
-def _stack_shape(flags):
-    J, d, V = flags["num_joints"], flags["embed_dim_ratio"], flags["num_views"]
-    if flags.get("FPT_blocks_view_keypoint_tokens"):
-        return J * V, d
-    return V, J * d * (2 if flags.get("input_rays_as_token") else 1)
 
 
 @pytest.mark.parametrize("name", sorted(FORWARD_MODELS))

@@ -7,12 +7,29 @@ mutex / event chain and error word.  tests/sanitize/run.sh compiles every transl
 C ABI without a GPU (every entry point must answer with an MPL_E_* code -- never a crash, an out-of-bounds access, a leak or
 undefined behaviour).  First run of this job (round 6): mpl_fpt_width(NULL) dereferenced its argument."""
 import os
+import re
 import shutil
 import subprocess
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _called_names(text):
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", "", text)
+    return set(re.findall(r"\b(mpl_[a-z0-9_]+)\s*\(", text))
+
+
+def test_the_driver_names_every_declared_entry_point():
+    """The job below is only as wide as tests/sanitize/host_driver.cpp: every `mpl_*(` that include/mpl_hip.h declares is
+    called there (comments do not count), with no list of exemptions, so an entry point added to the ABI without its walk turns
+    this red."""
+    declared = _called_names(open(os.path.join(ROOT, "include", "mpl_hip.h")).read())
+    driven = _called_names(open(os.path.join(ROOT, "tests", "sanitize", "host_driver.cpp")).read())
+    assert len(declared) >= 77
+    assert sorted(declared - driven) == []
 
 
 @pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"), reason="hipcc not available")
