@@ -13,7 +13,8 @@
 //   openmpl_amd::lift(h, poses, rays, centers, flags) -> Tensor   validates the V view tensors exactly as the Python route does
 //                                     (RuntimeError, same messages), allocates workspace + output through torch's caching
 //                                     allocator on the inputs' device, calls mpl_forward on c10::hip::getCurrentHIPStream.
-//                                     An UNDEFINED-size answer (0-d tensor of -1) = the binding is stale: Python re-marshals.
+//                                     An UNDEFINED-size answer (0-d tensor of -1) = the binding is stale, or no longer alive
+//                                     (released by a re-marshal on another route): Python re-marshals and binds again.
 //   openmpl_amd::unbind(h)            drops a binding (the parameter tensors and derived operands it kept alive).
 //
 // The entry points of libmpl_hip.so are handed over as addresses (openmpl_amd::set_entry_points, from the ctypes binding): this file
@@ -70,11 +71,11 @@ std::mutex g_mu;
 std::unordered_map<int64_t, std::shared_ptr<Binding>> g_bindings;
 int64_t g_next = 1;
 
+// nullptr: no such binding (released by a re-marshal on another route, or never made): lift() answers "stale"
 std::shared_ptr<Binding> lookup(int64_t h) {
     std::lock_guard<std::mutex> g(g_mu);
     auto it = g_bindings.find(h);
-    TORCH_CHECK(it != g_bindings.end(), "openmpl_amd::lift: binding ", h, " is not alive");
-    return it->second;
+    return it == g_bindings.end() ? nullptr : it->second;
 }
 
 void set_entry_points(int64_t forward_addr, int64_t ws_bytes_addr, int64_t errstr_addr, int64_t abi) {
@@ -156,6 +157,7 @@ at::Tensor stale_answer() { return at::full({}, -1, at::TensorOptions().dtype(at
 
 at::Tensor lift(int64_t h, at::TensorList poses, at::TensorList rays, at::TensorList centers, int64_t flags) {
     std::shared_ptr<Binding> b = lookup(h);
+    if (!b) return stale_answer();             // an unknown handle is a stale one: the caller marshals and binds again
     // ---- is the struct of addresses still what the module holds?  (moved storage: any tensor; changed values: folded tensors)
     for (size_t i = 0; i < b->params.size(); ++i) {
         const at::Tensor& t = b->params[i];

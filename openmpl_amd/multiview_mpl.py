@@ -50,6 +50,29 @@ except Exception:                       # an older torch without the global hook
     _HOOKS_OK = False
 
 
+# The fused optimizers (torch.optim.* with fused=True) update the parameters in ONE kernel that does not bump their version
+# counters (torch 2.10: _version 0 -> 0 after step(), on the CPU and on the GPU alike), so neither the address nor the version of a
+# folded tensor tells that its values changed.  A process-wide post-step hook counts the steps of fused optimizers instead; the
+# count is part of the key of the packed operands (_derived_key), and _STRUCT_GEN moves with it so that the extension shortcut
+# (_forward_fast) comes back to _marshal.  Steps of the for-loop and foreach implementations bump the versions and are not counted.
+_VALUE_GEN = [0]
+
+
+def _fused_step_hook(optimizer, *_a, **_k):
+    if any(g.get("fused") for g in optimizer.param_groups):
+        _VALUE_GEN[0] += 1
+        _STRUCT_GEN[0] += 1
+    return None
+
+
+_OPT_HOOK_OK = True
+try:
+    from torch.optim.optimizer import register_optimizer_step_post_hook as _reg_step_hook
+    _reg_step_hook(_fused_step_hook)
+except Exception:                       # an older torch without global optimizer hooks: fused steps need weights_changed()
+    _OPT_HOOK_OK = False
+
+
 class _Container(nn.Module):
     """Holds parameters under the reference's attribute names; not callable on its own."""
 
@@ -164,12 +187,34 @@ def _unbind(handle: int):
 
 
 def _release_binding(ent):
+    """Drop the extension binding of a marshalled entry, and the finalizer that would have dropped it with the module."""
     if ent is not None and ent.get("bind") is not None:
+        fin = ent.pop("bind_fin", None)
+        if fin is not None:
+            fin.detach()
         _unbind(ent.pop("bind"))
 
 
 class MultiView_MPL(nn.Module):
-    """Constructor surface and parameter layout of the reference ``MultiView_MPL`` (:94-317)."""
+    """Constructor surface and parameter layout of the reference ``MultiView_MPL`` (:94-317).
+
+    Which weights a forward runs on.  The kernels read most tensors in place; the Linear layers of the blocks run from packed
+    operands folded from the parameter VALUES (derived data, per device).  A forward notices by itself, through the address and
+    the version counter of the module's own tensors, exactly these updates and re-folds what they touch:
+    (a) an in-place op on a parameter or buffer under ``no_grad`` (``mul_``, ``add_``, ``copy_``); (b) the same on
+    ``p.detach()``; (c) ``p.data = other_storage``; (d) ``optimizer.step()`` (SGD, AdamW; for-loop, foreach and fused -- a
+    fused step leaves the version counters alone and is noticed through a process-wide optimizer post-step hook instead);
+    (e) ``load_state_dict`` (default and ``assign=True``); (f) assignment of a new ``nn.Parameter`` or submodule;
+    (g) ``torch.utils.swap_tensors``; (h) ``.cpu()`` / ``.to(device)`` / ``.double().float()``; (i) ``requires_grad_``
+    (which changes nothing).
+    NOT noticed: a write that leaves both the version counter and the address of the parameter untouched -- through
+    ``p.data`` (``p.data.mul_``, ``p.data.copy_``, ``torch._foreach_mul_([p.data, ...])``), through a view of foreign storage
+    (the flat vector the parameters view into after ``vector_to_parameters``-style flattening), by raw pointer, or by an
+    optimizer step replayed inside a captured graph (no Python runs, no counter moves).  ``torch.utils.swap_tensors`` on a
+    module that holds a live extension binding is refused by torch itself (the binding references the parameters; torch
+    wants to be their only owner): ``weights_changed()`` BEFORE the swap releases them.  Such a
+    write must be followed by ``weights_changed()`` before the next forward; without it the forward runs the old packed
+    operands: finite poses of the old weights, no error."""
 
     def __init__(self, num_joints=17, in_chans=2, embed_dim_ratio=32, depth=4, num_heads=8, mlp_ratio=2.0,
                  qkv_bias=True, qk_scale=None, drop_rate=0.0, attn_drop_rate=0.0, drop_path_rate=0.2,
@@ -471,6 +516,16 @@ class MultiView_MPL(nn.Module):
         self._hip_cache = {}
         self.__dict__["_fast_bind"] = {}
 
+    def weights_changed(self):
+        """Tell the module that parameter or buffer VALUES changed in a way a forward cannot notice (see the class docstring:
+        writes through ``.data``, through a view of foreign storage, by raw pointer).  Forgets every struct of addresses, packed
+        operand and extension binding on all devices; the next forward folds the operands again from the live tensors.
+        Returns self.  Calling it when nothing changed costs one re-pack and changes no bit of the result."""
+        self._drop_caches()
+        self.__dict__.pop("_tl_cache", None)
+        self.__dict__.pop("_x3_ok", None)
+        return self
+
     def _replicate_for_data_parallel(self):
         """DataParallel replicas (valid_mpl.py:177-178) are shallow copies that torch re-creates on EVERY forward with freshly
         broadcast parameter storage.  The packed operands are derived from the parameter VALUES, which are the source module's:
@@ -543,7 +598,7 @@ class MultiView_MPL(nn.Module):
         src = self._dp_src if self._dp_replica else self
         _, fpt, spt = src._tensor_lists()
         ts = (fpt if (h2 or bf16 or d32) else []) + (spt if spt3 else [])
-        return (self.matmul_precision, h2, bf16, spt3, d32) + tuple([(t.data_ptr(), _ver(t)) for t in ts])
+        return (self.matmul_precision, h2, bf16, spt3, d32) + tuple([(t.data_ptr(), _ver(t)) for t in ts]) + (_VALUE_GEN[0],)
 
     def _marshal(self, device: torch.device):
         """Build (and cache per device) the mpl_weights struct.  Parameters are consumed in place, so the struct stays valid
@@ -658,7 +713,9 @@ class MultiView_MPL(nn.Module):
             # the packing kernels ran on THIS stream: the event and the stream stay with the derived operands, which outlive the
             # struct when only addresses change (DataParallel replicas) -- a later forward on another stream waits for it too
             derived["ready"], derived["stream"] = new["ready"], st
-        _release_binding(ent)                  # the extension binding of the entry this one replaces
+        _release_binding(ent)                  # the extension binding of the entry this one replaces ...
+        # ... and the shortcut that names it: a dead handle must not be lifted again (a replica shares the SOURCE's cache)
+        (self._dp_src if self._dp_replica and self._dp_src is not None else self)._fast_bind.pop(device.index, None)
         self._hip_cache[device.index] = new
         return new
 
@@ -684,7 +741,9 @@ class MultiView_MPL(nn.Module):
                          torch_ext.struct_bytes(ent["fpt_blocks"]), list(plist), versioned, keep, dev.index, needs_rays))
         torch_ext._FAKE_SHAPES[h] = self.num_joints
         ent["bind"] = h
-        _weakref.finalize(self, _unbind, h)       # a module that dies without being cleared must not pin its parameters in C++
+        # a module that dies without being cleared must not pin its parameters in C++; the finalizer goes with the binding
+        # (_release_binding), so a module that re-binds after every weight update carries one, not one per update
+        ent["bind_fin"] = _weakref.finalize(self, _unbind, h)
         return h
 
     def _forward_fast(self, poses, rays, centers):
@@ -695,9 +754,13 @@ class MultiView_MPL(nn.Module):
         if t0 is None or not t0.is_cuda or self.training:
             return None
         flags = 0 if self._small_engine_allowed() else cabi.F_NO_SMALL_STACK
+        # the routes accept the same containers: a stacked (V,B,J,3) tensor or any sequence, as _check_inputs does
+        poses = list(poses)
+        rays = () if rays is None else list(rays)
+        centers = () if centers is None else list(centers)
         f = self._fast_bind.get(t0.device.index)
         if f is not None and f[1] == _STRUCT_GEN[0] and all(a is b for a, b in zip(f[2], self._tl_probe())):
-            out = _EXT_LIFT[0](f[0], poses, rays or (), centers or (), flags)
+            out = _EXT_LIFT[0](f[0], poses, rays, centers, flags)
             if out.dim() != 0:
                 return out
         # no binding for this device yet, or a parameter moved / changed: marshal (the slow, complete check) and bind again
@@ -715,7 +778,7 @@ class MultiView_MPL(nn.Module):
             if h is None:
                 h = self._bind(ent, dev)
         self._fast_bind[dev.index] = (h, _STRUCT_GEN[0], self._tl_probe())
-        out = _EXT_LIFT[0](h, poses, rays or (), centers or (), flags)
+        out = _EXT_LIFT[0](h, poses, rays, centers, flags)
         if out.dim() == 0:
             raise RuntimeError("openmpl_amd::lift reports a stale binding right after it was made (a parameter is being modified "
                                "concurrently with the forward)")
@@ -1013,6 +1076,10 @@ class MultiView_MPL_G(nn.Module):
 
     def use_torch_op(self, mode="auto"):
         self.features.use_torch_op(mode)
+        return self
+
+    def weights_changed(self):
+        self.features.weights_changed()
         return self
 
     def init_weights(self, pretrained=""):

@@ -62,6 +62,19 @@ def _inputs(B, seed=1, V=4):
     return mk(p), mk(r), mk(c)
 
 
+class _Seq:
+    """A sequence that is neither a list nor a tuple."""
+
+    def __init__(self, items):
+        self._items = list(items)
+
+    def __len__(self):
+        return len(self._items)
+
+    def __getitem__(self, i):
+        return self._items[i]
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("B", [1, 8, 64, 300])
 def test_extension_route_is_bitwise_the_other_routes(B):
@@ -79,7 +92,17 @@ def test_extension_route_is_bitwise_the_other_routes(B):
         m.use_torch_op("auto")
         strided = [x.expand(2, *x.shape)[0] if i % 2 else x.clone().transpose(0, 1).contiguous().transpose(0, 1) for i, x in enumerate(P)]
         ext3 = m(strided, rays=R, centers=C)                           # non-contiguous views are made contiguous in C++
+        # every route accepts the same containers: a stacked (V,B,J,3) tensor, or any sequence that is no list (one whose truth
+        # value is ambiguous included: the stacked tensor raised "Boolean value of Tensor ... is ambiguous" on the default route)
+        sp, sr, sc = torch.stack(P), torch.stack(R), torch.stack(C)
+        containers = {}
+        for route in ("auto", True, False):
+            m.use_torch_op(route)
+            containers[route] = (m(sp, rays=sr, centers=sc), m(_Seq(P), rays=_Seq(R), centers=_Seq(C)), m(sp, rays=None, centers=None))
+        m.use_torch_op("auto")
     assert torch.equal(direct, ext) and torch.equal(direct, ext2) and torch.equal(direct, pyop) and torch.equal(direct, ext3)
+    for route, outs in containers.items():
+        assert all(torch.equal(direct, o) for o in outs), "containers on route %r" % (route,)
     torch.library.opcheck(torch.ops.openmpl_amd.lift, (m._fast_bind[0][0], P, R, C, 0),
                           test_utils=("test_schema", "test_faketensor", "test_autograd_registration"))
     with torch.no_grad(), torch.profiler.profile(activities=[torch.profiler.ProfilerActivity.CPU]) as prof:
